@@ -12,15 +12,20 @@ first-arrival travel-time fields (inputs resident in HBM, fields left resident i
 ray tracer reads them).  Sources are independent: no data-path collective; torch.distributed
 (gloo) only provides the barrier and the max over ranks of the step time.
 
-value = 128 x 4096^2 cell-updates x steps / max-over-ranks wall time of the timed steps.
+value = 128 x 4096^2 cell-updates x steps / max-over-ranks wall time of the timed steps;
+ms_per_step = that wall time / steps.  A plain run sets up, warms up, times the steps, writes
+--dump-outputs DIR (a fixed seeded sample of every field of the last step, DIR/fields.npy) and
+prints the result line; the legs below marked (--full) run after that with --full only and are
+null in a plain run's line.
 roofline: the band kernel (fmm_band_k_kernel), SURVEY §8(d)'s 18.1 algorithmic bytes per
 cell-sweep (one evaluation of the local operator, counted by the kernel) over the kernel's
-in-library HIP-event time on its stream; traffic = HBM bytes per launch from rocprofv3 PMC
+in-library HIP-event time on its stream; (--full) traffic = HBM bytes per launch from rocprofv3 PMC
 passes of the same library build (profiles/*_traffic.json), with traffic / algorithmic.
-result_return: after the timed steps, the fields' way back (not in value): D2H into pageable
+result_return (--full): after the timed steps, the fields' way back (not in value): D2H into pageable
 host memory through the library's pinned staging ring, every rank at once; with --gather (N > 1)
 also an RCCL gather of every rank's fields to rank 0 over xGMI.
-cpu_baseline: the CPU restatement of the reference (oracle/, one source per thread) on a bounded
+update_end_to_end, c5, c3 (--full): see the functions below.
+cpu_baseline (--full): the CPU restatement of the reference (oracle/, one source per thread) on a bounded
 sample, rank 0, N = 1.
 """
 import argparse
@@ -64,7 +69,40 @@ def parse():
     ap.add_argument("--members", type=int, default=None, help="band-kernel workgroups per source (0: auto)")
     ap.add_argument("--cdelta", type=float, default=None)
     ap.add_argument("--no-c5", action="store_true", help="skip the BASELINE config 5 leg (receiver fields + rays)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline figure: profiled traffic, "
+                         "result return, end-to-end update(), C5, C3 and the CPU baseline (the --no-* flags and "
+                         "--gather select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed step's fields to DIR/fields.npy "
+                         "(DIR/fields_rank<r>.npy when N > 1)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 48 << 20  # all ranks' dumps together (float64)
+DUMP_SEED = 20240
+
+
+def dump_cells(cells, total_src):
+    """Flat indices (ascending) of the cells --dump-outputs keeps of every field: a seeded draw
+    without replacement, DUMP_BYTES / 8 / total_src of them (all cells when they fit)."""
+    m = min(cells, max(1, DUMP_BYTES // 8 // max(1, total_src)))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(cells, size=m, replace=False))
+
+
+def dump_outputs(ctx, args, ns, total_src, rank, world):
+    """--dump-outputs: what the last timed step left resident, the rank's ns travel-time fields
+    (subgrid 1, slots 0 .. ns-1), as one float64 (ns, m) array: the same m cells (dump_cells) of
+    every field.  The draw depends on the grid and the total number of sources only, so two builds
+    run with the same arguments write the same cells of the same sources."""
+    fz, fx = ctx.field_shape(1)
+    idx = dump_cells(fz * fx, total_src)
+    out = np.empty((ns, len(idx)), dtype=np.float64)
+    for i in range(ns):
+        out[i] = ctx.get_field(i, 1).reshape(-1)[idx]
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    name = "fields.npy" if world == 1 else "fields_rank%d.npy" % rank
+    np.save(os.path.join(args.dump_outputs, name), out)
 
 
 _COUNT_GPUS = r"""
@@ -470,6 +508,9 @@ def main():
                           % (n, n, total_src, "per GPU (weak)" if args.weak else "dealt over the GPUs (strong)"),
               "total_sources": total_src, "sources_per_gpu": ns, "grid": [n, n], "subgrid": 1,
               "band_workgroups_per_source": members, "cdelta": args.cdelta}
+    if args.dump_outputs:
+        dump_outputs(ctx, args, ns, total_src, rank, world)
+    # the legs from here to the result line run with --full only
     # HBM-side bytes per launch: rocprofv3 PMC passes (tools/profile.sh) on this library and workload
     traffic_bytes = None
     valu = None
@@ -477,8 +518,9 @@ def main():
         import glob
         import hashlib
 
-        lib_sha = hashlib.sha256(open(_alifmm.LIB_PATH, "rb").read()).hexdigest()
-        for f in sorted(glob.glob(os.path.join(REPO, "profiles", "*_traffic.json"))):
+        profiled = sorted(glob.glob(os.path.join(REPO, "profiles", "*_traffic.json"))) if args.full else []
+        lib_sha = hashlib.sha256(open(_alifmm.LIB_PATH, "rb").read()).hexdigest() if profiled else None
+        for f in profiled:
             t = json.load(open(f))
             if (t.get("libalifmm_sha256") == lib_sha and t.get("traffic_bytes_per_launch")
                     and t.get("kernel", "fmm_band_k_kernel") == "fmm_band_k_kernel"
@@ -491,7 +533,7 @@ def main():
 
     # result-return leg (not in value): D2H of this rank's fields; RCCL gather to rank 0 (N > 1)
     ret = None
-    if not args.no_return:
+    if args.full and not args.no_return:
         ret = {}
         barrier()
         t1 = time.perf_counter()
@@ -515,7 +557,7 @@ def main():
     # fields, and their single copy into the caller's (nsrc, 4096, 4096) stack; the second call is
     # timed (the first uploads the model into the object's own context)
     e2e = None
-    if world == 1 and not args.no_e2e:
+    if args.full and world == 1 and not args.no_e2e:
         import Anis_TTF_rays as A
 
         ctx.release_fields()
@@ -540,13 +582,13 @@ def main():
         for c in M._ctxs.values():
             c.close()
     c5 = None
-    if not args.no_c5:
+    if args.full and not args.no_c5:
         c5 = c5_leg(ctx, rank, world, dist, n, dnx, barrier)
     c3 = None
-    if world == 1 and not args.no_c3:
+    if args.full and world == 1 and not args.no_c3:
         c3 = c3_line(ctx, W)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(args, scx, scz, model, vt, dnx, cells)
     if rank == 0:
         out = {

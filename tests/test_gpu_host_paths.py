@@ -118,3 +118,37 @@ def test_option_environment_hook(monkeypatch):
         assert c.get_option("cdelta") == 0.5  # the bad value left the default
     finally:
         c.close()
+
+
+def test_bench_plain_run_dumps_its_fields(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps, reports ms_per_step, leaves
+    the legs beside the headline figure out of its line, and --dump-outputs writes the same seeded
+    cells of every field of the last step as float64 (two C4 sources here)."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "ALIFMM_BENCH_DEVICE",
+                                                            "ALIFMM_BENCH_STUB")}
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0",
+                        "--sources", "2", "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["warmup"] == 0 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(2 * 4096.0 ** 2 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["unit"] == "grid-cell updates/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    for leg in ("result_return", "update_end_to_end", "c3", "c5", "cpu_baseline"):
+        assert line[leg] is None, leg
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["fields.npy"]
+    F = np.load(tmp_path / "out" / "fields.npy")
+    assert F.dtype == np.float64 and F.ndim == 2 and F.shape[0] == 2 and F.nbytes <= 64e6
+    assert np.all(np.isfinite(F)) and F.min() >= 0 and F.max() > 0
+    assert not np.array_equal(F[0], F[1])  # two sources, the same cells
+    # the sampled cells depend on the arguments only
+    import bench
+
+    idx = bench.dump_cells(4096 * 4096, 2)
+    assert F.shape[1] == len(idx) and np.all(np.diff(idx) > 0) and np.array_equal(idx, bench.dump_cells(4096 * 4096, 2))
