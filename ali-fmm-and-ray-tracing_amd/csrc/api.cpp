@@ -299,6 +299,7 @@ int alifmm_set_option(alifmm_ctx* ctx, const char* name, double value) {
   else if (!strcmp(name, "members") && value >= 0 && value <= af::kMaxK && value == (int)value)
     ctx->members = (int)value;
   else if (!strcmp(name, "stripe_log") && (value == 0 || (value >= 3 && value <= 12))) ctx->stripe_log = (int)value;
+  else if (!strcmp(name, "xcd_local")) ctx->xcd_local = value != 0;
   else return fail(ctx, ALIFMM_E_ARG, "unknown option or bad value: %s=%g", name, value);
   return ALIFMM_OK;
 }
@@ -322,6 +323,7 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "coop")) *value = ctx->coop;
   else if (!strcmp(name, "members")) *value = ctx->members;
   else if (!strcmp(name, "stripe_log")) *value = ctx->stripe_log;
+  else if (!strcmp(name, "xcd_local")) *value = ctx->xcd_local;
   else if (!strcmp(name, "last_k")) *value = ctx->last_k;
   else if (!strcmp(name, "n_cu")) *value = ctx->n_cu;
   else if (!strcmp(name, "vmax")) *value = ctx->vmax;  // model's fastest speed (set_model; the exact-walk stop)
@@ -611,10 +613,21 @@ int af_ensure_field(alifmm_ctx* ctx, int slot, int sg, int fz, int fx, long extr
 
 // members per source of the band kernel: the largest K <= kMaxK whose grid (nsrc padded to 8, times
 // K workgroups, af_band_wgs_per_cu() of them per CU) is co-resident, with >= 2 stripes per member
-// (option "members" forces a value, still capped by residency)
+// (option "members" forces a value, still capped by residency and by the stripe count: a member
+// without a stripe would only take its 1 / K share of the work lists, travel_chunk capL / K, from
+// the members that own cells)
 static int choose_members(const alifmm_ctx* ctx, int n, int fx) {
   const int by_cu = std::max(1, ctx->n_cu * af_band_wgs_per_cu() / (8 * ((n + 7) / 8)));
-  if (ctx->members > 0) return std::max(1, std::min(ctx->members, by_cu));
+  if (ctx->members > 0) {
+    int K = std::max(1, std::min(ctx->members, by_cu));
+    // the stripe width follows K (travel_chunk) unless "stripe_log" fixes it: lower K until it fits
+    for (;;) {
+      const int wlog = ctx->stripe_log ? ctx->stripe_log : (K >= 16 ? 4 : K >= 8 ? 5 : 6);
+      const long nstr = ((long)fx + (1L << wlog) - 1) >> wlog;
+      if (K <= nstr) return K;
+      K = (int)nstr;
+    }
+  }
   // >= 2 stripes per member at the stripe width the member count selects
   auto stripes = [&](int k) { return (long)(fx + (1 << (k >= 8 ? 4 : 6)) - 1) >> (k >= 8 ? 4 : 6); };
   int K = std::min(af::kMaxK, by_cu);
@@ -771,6 +784,7 @@ static int travel_chunk(alifmm_ctx* ctx, int sg, int n, const double* scx, const
   P.coop = ctx->coop;
   P.K = K;
   P.wlog = wlog;
+  P.xcd_local = ctx->xcd_local;
   P.capR = (int)capR;
   P.ecells = ecells;
   P.tb_pitch = af_band_tb_pitch(fx);

@@ -104,6 +104,7 @@ struct alifmm_ctx {
   int members = 0;     // band kernel: workgroups per source (0: as many as the device fits, <= 16)
   int stripe_log = 0;  // band kernel: stripe width log2 (0: 6 for K <= 4, 4 for K >= 8)
   int last_k = 0;      // members per source of the last band launch
+  int xcd_local = 1;   // band kernel: plain cross-member stores once a source's members share an XCD (0: always sc1)
   int n_cu = 0;
   long cap_scale = 1;
   // state

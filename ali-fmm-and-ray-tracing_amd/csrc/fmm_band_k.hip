@@ -622,7 +622,8 @@ AF_DEV void publish_tiles(Lds* sh, const TileStream& ts, int b, int lane) {
 // and exchange words are stored plainly instead of write-through (sc1): the stores complete in the
 // XCD's L2, which the readers' sc1 (L1-bypassing) loads are served from, instead of travelling to
 // memory and dropping the line from L2.  Placement is read, not assumed: members on different XCDs
-// keep the sc1 stores (MI355X_MICROARCH.md "inter-workgroup visibility").
+// keep the sc1 stores (MI355X_MICROARCH.md "inter-workgroup visibility").  BandParams::xcd_local 0
+// (option "xcd_local") keeps them on one XCD as well: the write-through exchange under test.
 #ifndef AF_XCD_LOCAL
 #define AF_XCD_LOCAL 1
 #endif
@@ -637,7 +638,7 @@ AF_DEV void xst(T* p, T v, bool loc) {
   else gst_sc1(p, v);
 }
 
-AF_DEV bool x1_poll(KX* X, int K, int par, unsigned tag, Lds* sh, int mprev, int mnext) {
+AF_DEV bool x1_poll(KX* X, int K, int par, unsigned tag, Lds* sh, int mprev, int mnext, int xcd_local) {
   const int lane = threadIdx.x & 63;
   const int nw = 4 * K;
   unsigned long long v = 0;
@@ -676,7 +677,7 @@ AF_DEV bool x1_poll(KX* X, int K, int par, unsigned tag, Lds* sh, int mprev, int
     sh->tmin_g = tmin;
     sh->live_g = live;
     sh->err_g = err;
-    sh->xl = same ? 1 : 0;
+    sh->xl = same && xcd_local;
   }
   return true;
 }
@@ -891,7 +892,7 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
   R.tfar = P.r_far > 0 && P.cdelta_far > 0 ? P.r_far * P.dnx / P.vmax : 0.0;
   long long steps = 0, myupd = 0;
   // profile (P.prof): thread 0 of member 0; phases [P1 + X1, accept + rim read, claim,
-  // evaluate, fallback, commit], sub [X1 wait, rim read, claim dedupe, drain before X1]
+  // evaluate, fallback, commit], sub [X1 wait, rim read, XCD-local steps x 100, drain before X1]
   const bool prof = PROF && tid == 0 && me == 0;
   long long ph[6] = {0, 0, 0, 0, 0, 0}, sub[4] = {0, 0, 0, 0}, ls[3] = {0, 0, 0}, lmax = 0;
   long long tk = prof ? wall_clock64() : 0;
@@ -988,7 +989,7 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
         xst(&X->x1[me][par][2], gtag | ((unsigned)xcc_id() << 28) | ((unsigned)(hi - sh->nF) & 0x0fffffffu), loc);
         xst(&X->x1[me][par][3], gtag | ((unsigned)min(sh->err, 255) << 24) | (unsigned)min(sh->nRb[par], 0xffffff), loc);
       }
-      if (wv == 0 && !x1_poll(X, K, par, (unsigned)(steps + 1), sh, mprev, mnext)) {
+      if (wv == 0 && !x1_poll(X, K, par, (unsigned)(steps + 1), sh, mprev, mnext, P.xcd_local)) {
         if (lane == 0) sh->err = 7;
       }
     } else if (tid == 0) {
@@ -1004,6 +1005,9 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
 #endif
     AF_TICK(0)
     if (sh->live_g <= 0 || sh->err_g || sh->err) break;
+#if !AF_PROF_CLAIM && !AF_PROF_SEG && !AF_PROF_EVW
+    if (prof) sub[2] += sh->xl ? 100 : 0;  // steps whose exchange was XCD-local (x 100; of steps[3])
+#endif
     // ---- P0: last step's accepted edge cells into this step's edge buffer.  Only now: every member
     // has passed this step's X1, i.e. finished the previous step, which read this buffer.  The
     // list is the last step's parity (this step's acceptance fills the other one: no barrier) ----

@@ -837,7 +837,9 @@ __global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* job
     // the wavefront hits grid edges and close hand-over nodes get overwritten.  Run it exactly
     // until the root's T reaches exact_r*dnx/vmax (or the root comes within 3 nodes of a window
     // edge that is not a grid edge), then hand the heap's state to the band kernel.
-    const int W = J.exact_r + 6;
+    // The window also holds the whole stage-3 hand-over (13 nodes around the source), 3 nodes
+    // inside its edges as above: exact_r < 10 widens it (the walk then stops at its first root).
+    const int W = max(J.exact_r + 6, 13 + 3);
     const int wz0 = (int)max(0L, isz - W), wz1 = (int)min((long)nnz - 1, isz + W);
     const int wx0 = (int)max(0L, isx - W), wx1 = (int)min((long)nnx - 1, isx + W);
     const int wh = wz1 - wz0 + 1, ww = wx1 - wx0 + 1;

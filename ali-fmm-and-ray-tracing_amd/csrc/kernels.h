@@ -78,6 +78,7 @@ struct BandParams {
   int coop;  // 1: hipLaunchCooperativeKernel (default); 0: plain launch after a residency check (under rocprofv3)
   int K;     // fmm_band_k: members per source (power of two <= kMaxK)
   int wlog;  // fmm_band_k: stripe width log2
+  int xcd_local;  // fmm_band_k: 1 = plain cross-member stores once every member reports one XCD; 0 = always sc1
   int capR;  // fmm_band_k: rim-list capacity per member and parity
   long ecells;  // fmm_band_k: cells per edge buffer
   int tb_pitch;   // fmm_band_k: working-field pitch (bricks per brick row, or row pitch)

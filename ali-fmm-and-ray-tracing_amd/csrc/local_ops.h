@@ -822,7 +822,9 @@ AF_DEV double lane_d(double v, int l) {
 AF_DEV bool update_select_lanes(double tk, bool vk, AF_UPD_IDX iz, AF_UPD_IDX ix, AF_UPD_IDX nnz, AF_UPD_IDX nnx,
                                 int lane, UpdSel& r) {
     using I = AF_UPD_IDX;
-    if (ix == 0 || ix == nnx - 1 || iz == 0 || iz == nnz - 1) return false;
+    // (>=: stage 1 passes update() its nnx as nnz for close x-neighbours, :1645, so on a grid with
+    // more rows than columns a node can lie past the bound; update_nb_select() masks its lower slots)
+    if (ix == 0 || ix >= nnx - 1 || iz == 0 || iz >= nnz - 1) return false;
     // interior: every position of the 12 is inside the operator's bounds (update_nb_select's inb)
     const bool r2 = ix < nnx - 2, l2 = ix > 1, u2 = iz > 1, d2 = iz < nnz - 2;
     const unsigned inb = 2u | 4u | 32u | 64u | 256u | 512u | 1024u | 2048u | (l2 ? 1u : 0u) | (r2 ? 8u : 0u) |

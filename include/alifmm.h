@@ -48,8 +48,12 @@ int alifmm_set_model(alifmm_ctx* ctx, int nnz, int nnx, const double* veln, cons
                      const double* phase_tab, int ncol, double dnx, double dnz, double gox, double goz);
 
 /* Tuning: "members" (workgroups per source of the band kernel: 0 = as many as the device holds
- * for the batch, else 1 .. 16; results are bit-identical for every value), "stripe_log"
- * (column-stripe width log2 of the band kernel's ownership, 0 = automatic), "prof" (1: record the
+ * for the batch, else 1 .. 16, lowered to the number of column stripes on a narrow grid; results
+ * are bit-identical for every value), "stripe_log"
+ * (column-stripe width log2 of the band kernel's ownership, 0 = automatic), "xcd_local" (1, the
+ * default: once every member of a source reports the same XCD, the cross-member exchange stores
+ * plainly into that XCD's L2; 0: always write-through (sc1) stores, the path members on different
+ * XCDs take; bit-identical), "prof" (1: record the
  * band profile, alifmm_band_profile), "cdelta" (band width in units of dnx/vmax; unset, the
  * library chooses it per model: 0.5, narrowed down to 0.2 where the materials change from cell to
  * cell — fraction of neighbour pairs with different materials ("mat_jump", / subgrid) from 0.3 to
@@ -144,8 +148,10 @@ int alifmm_last_timing(alifmm_ctx* ctx, double* init_ms, double* band_ms, double
 /* Band-kernel profile of a slot's last alifmm_travel() when option "prof" is 1 (zeros otherwise):
  * out14[0..5] wall-clock ticks (100 MHz) spent by the workgroup in the step phases [Tmin, accept,
  * claim, evaluate, fallback, commit]; out14[6..8] sums over steps of the close / accepted /
- * evaluated list sizes; out14[9] the largest close set; out14[10..13] thread 0's ticks inside
- * phases: claim [neighbour + dedupe, nsts loads, list pushes], evaluate [neighbourhood loads]. */
+ * evaluated list sizes; out14[9] the largest close set; out14[10], [11], [13] thread 0's ticks
+ * inside phases (wait for the cross-member exchange, neighbour rim-list read, drain before the
+ * exchange); out14[12] 100 x the main-loop steps (alifmm_source_stats steps4[3]) whose exchange
+ * stored XCD-locally (every member on one XCD; always 0 with option "xcd_local" 0 or one member). */
 int alifmm_band_profile(alifmm_ctx* ctx, int slot, int64_t* out14);
 /* Wall clock (100 MHz ticks) at which the band kernel's first member of the slot's source started
  * and finished in the last alifmm_travel(): out2[0], out2[1] (dispatch and load-balance diagnostic). */

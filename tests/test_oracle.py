@@ -196,3 +196,36 @@ def test_notebook_kats(golden):
     for ij, tp in pub.items():
         assert r[ij][2] == g["k3_times"][ij]
         assert abs(r[ij][2] - tp) / tp < 5e-7
+
+
+def test_band_case_matrix_preconditions():
+    """What tests/test_gpu_band_small.py relies on, from the oracle alone (tests/band_cases.py): the
+    CPU band model's field of every case and source of the matrix is finite and positive in every
+    cell but the source (so the GPU test compares all cells, none masked); the models' material
+    counts lie in the classes they are named for; the far-band case differs from the one-width
+    field; a grid origin changes no bit; the dnz != dnx case runs."""
+    import band_cases as BC
+
+    for model in BC.MODELS:
+        nz, nx = BC.MODEL_SHAPE[model]
+        lo, hi = BC.MATERIAL_CLASS[model]
+        assert lo <= BC.material_count(model, nz, nx) <= hi, model
+    assert BC.material_count("many_mid", 61, 65) == 61 * 65 and BC.material_count("many_big", 97, 129) == 97 * 129
+    # the band widths the library will pick: the default on one record and on grains, the narrow
+    # one where the material changes from cell to cell
+    assert BC.lib_options(BC.MODEL_CASES[0])["cdelta"] == 0.5 and BC.lib_options(BC.MODEL_CASES[1])["cdelta"] == 0.5
+    for c in BC.MODEL_CASES[2:]:
+        assert BC.lib_options(c)["cdelta"] == 0.2, c.name
+    todo = BC.all_oracle_cases()
+    assert len(set((c.name, s) for c, s in todo)) >= 300
+    for c, s in todo:
+        B = BC.model_field(c, s)
+        assert B.shape == (c.nz, c.nx) and np.isfinite(B).all(), (c.name, s)
+        assert B[s[1], s[0]] == 0.0 and (np.delete(B.ravel(), s[1] * c.nx + s[0]) > 0).all(), (c.name, s)
+    far, one = BC.model_field(BC.FAR_CASE, BC.FAR_SOURCE), BC.model_field(BC.FAR_OFF_CASE, BC.FAR_SOURCE)
+    assert int(np.sum(far != one)) > 10000  # the far band engages on most of the 129 x 129 grid
+    for k in BC.PARAM_SOURCES:
+        s = BC.sources(*BC.DEFAULT_SHAPE)[k]
+        assert np.array_equal(BC.model_field(BC.ORIGIN_CASE, s), BC.model_field(BC.ORIGIN_ZERO, s)), s
+    dz = [c for c in BC.PARAM_CASES if c.dnz != c.dnx]
+    assert len(dz) == 1 and dz[0].dnz == 1.5e-3 and dz[0].dnx == 1e-3

@@ -15,30 +15,7 @@ sys.path.insert(0, os.path.join(REPO, "oracle"))
 sys.path.insert(0, os.path.join(REPO, "tests"))
 import oracle as O  # noqa: E402
 import workloads as W  # noqa: E402
-
-
-def vmax_of(velpn, vm, sd, vt):
-    """api.cpp set_model's vmax: the fastest group velocity over the model."""
-    ang = 0.05 * np.arange(3601)
-    rows = {}
-    v = 0.0
-    for i in np.ndindex(velpn.shape):
-        if velpn[i] != 0:
-            v = max(v, vt[:181, velpn[i]].max() * vm[i])
-        else:
-            key = tuple(sd[i])
-            if key not in rows:
-                rows[key] = max(O.group_vel(a, *[float(k) for k in key]) for a in ang)
-            v = max(v, rows[key] * vm[i])
-    return v
-
-
-def jump_density(veln, velpn, vm, sd):
-    """Fraction of 4-neighbour pairs whose materials differ (api.cpp material_jump)."""
-    key = np.stack([veln, vm, velpn.astype(np.float64)] + [sd[..., k].astype(np.float64) for k in range(5)], -1)
-    dh = np.any(key[:, 1:] != key[:, :-1], -1)
-    dv = np.any(key[1:, :] != key[:-1, :], -1)
-    return float((dh.sum() + dv.sum()) / (dh.size + dv.size))
+from band_cases import jump_density, vmax_of  # noqa: E402
 
 
 def models(n):
