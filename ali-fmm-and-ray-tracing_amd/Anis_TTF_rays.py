@@ -590,6 +590,39 @@ class ALI_FMM:
         res = self._fields(veln, velpn, vel_map, stif_den, subgrid_size, [source_i], [0])
         return res[source_i][2]
 
+    def tfm(self, fmc, fs, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1, veln=None,
+            velpn=None, vel_map=None, stif_den=None):
+        """Total-focusing-method image of full-matrix-capture data fmc[(a, b, t)] with the
+        first-arrival travel-time fields as delay laws: I(p) = sum_ab w_ab s_ab(T_a(p) + T_b(p))
+        (no counterpart in the reference, whose fields exist for this purpose).
+
+        fmc: (len(tx), len(rx), nt) real RF or complex analytic data sampled at fs [Hz] from t0 [s].
+        tx, rx: element indices into scx, scz (default: all).  weights: (len(tx), len(rx))
+        apodisation or 0/1 pair mask.  window = (iz0, ix0, niz, nix) in pixels of `step` fine-grid
+        nodes; None: the whole field.  Model arguments default to the object's stored arrays.
+        The fields of the union of the elements are computed and left on the device, the
+        delay-and-sum reads them there (_alifmm.Context.tfm), and only the image comes back:
+        float64 (niz, nix), or complex128 for complex data.
+
+        One GPU (device 0) only: every GPU would need every field, and sharding the pixels over
+        GPUs is not implemented."""
+        veln = self.veln if veln is None else veln
+        velpn = self.velpn if velpn is None else velpn
+        vel_map = self.vel_map if vel_map is None else vel_map
+        if vel_map is None:
+            vel_map = np.ones(np.shape(veln))
+        stif_den = self.stif_den if stif_den is None else stif_den
+        tx = list(range(self.nsrc)) if tx is None else [int(i) for i in tx]
+        rx = list(range(self.nsrc)) if rx is None else [int(i) for i in rx]
+        for i in tx + rx:
+            if not 0 <= i < self.nsrc:
+                raise IndexError("tfm: element %d of %d" % (i, self.nsrc))
+        union = sorted(set(tx) | set(rx))
+        res = self._fields(veln, velpn, vel_map, stif_den, subgrid_size, union, [0], copy_out=False)
+        slot = {i: res[i][1] for i in union}
+        return self._ctx(0).tfm([slot[i] for i in tx], [slot[i] for i in rx], fmc, fs, t0=t0, weights=weights,
+                                window=window, step=step, subgrid=int(subgrid_size))
+
     def plot_phase(self, material_index=1):
         import matplotlib.pyplot as plt
 

@@ -80,6 +80,7 @@ def _load():
             "alifmm_band_span": (_i, [_p, _i, _p]),
             "alifmm_init_profile": (_i, [_p, _i, _p]),
             "alifmm_put_field": (_i, [_p, _i, _i, _p]),
+            "alifmm_tfm": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
             "alifmm_time_between_points": (_i, [_p, _i, _p, _p, _p, _p, _i, _p]),
             "alifmm_local_ops": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i,
                                       _p]),
@@ -296,6 +297,43 @@ class Context:
         if data.shape != self.field_shape(subgrid):
             raise ValueError("field shape %s does not match subgrid %d" % (data.shape, subgrid))
         self._chk(lib().alifmm_put_field(self._h, int(slot), int(subgrid), _ptr(data)), "put_field")
+
+    def tfm(self, tx_slots, rx_slots, fmc, fs, t0=0.0, weights=None, window=None, step=1, subgrid=1):
+        """Total-focusing-method image of full-matrix-capture data over resident fields
+        (alifmm_tfm): I(p) = sum_ab w_ab s_ab(T_a(p) + T_b(p)), linear interpolation in time, all
+        in float64; the fields stay on the device and one image comes back.
+
+        tx_slots, rx_slots: resident slots (of `subgrid`, one shape) of the transmitters' and
+        receivers' fields.  fmc: (ntx, nrx, nt) real RF or complex analytic data (any float or
+        complex dtype; sent as float32 / interleaved float32), sample k taken at t0 + k / fs.
+        weights: (ntx, nrx) or None.  window = (iz0, ix0, niz, nix) in pixels of `step` fine-grid
+        nodes from node (iz0, ix0); None: the whole field at that step.
+        Returns float64 (niz, nix), or complex128 for complex data."""
+        tx, rx = _ci32(np.atleast_1d(tx_slots)), _ci32(np.atleast_1d(rx_slots))
+        fmc = np.asarray(fmc)
+        if fmc.ndim != 3 or fmc.shape[:2] != (len(tx), len(rx)):
+            raise ValueError("fmc must have shape (ntx, nrx, nt) = (%d, %d, nt), not %s"
+                             % (len(tx), len(rx), fmc.shape))
+        cplx = np.iscomplexobj(fmc)
+        data = np.ascontiguousarray(fmc, dtype=np.complex64 if cplx else np.float32)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != fmc.shape[:2]:
+                raise ValueError("weights must have shape (ntx, nrx)")
+        step = int(step)
+        if window is None:
+            if step < 1:
+                raise AlifmmError("tfm: step %d" % step)
+            fz, fx = self.field_shape(subgrid)
+            window = (0, 0, (fz - 1) // step + 1, (fx - 1) // step + 1)
+        iz0, ix0, niz, nix = (int(v) for v in window)
+        nc = 2 if cplx else 1
+        img = np.empty((max(niz, 0), max(nix, 0), nc))
+        self._chk(lib().alifmm_tfm(self._h, int(subgrid), len(tx), _ptr(tx), len(rx), _ptr(rx), _ptr(data),
+                                   fmc.shape[2], nc, float(t0), float(fs), _ptr(w), iz0, ix0, niz, nix, step,
+                                   _ptr(img)), "tfm")
+        return img.view(np.complex128)[..., 0] if cplx else img[..., 0]
 
     def copy_fields(self, first_slot, n, subgrid, out=None, dst_kind=0):
         """Resident fields of slots first_slot .. first_slot+n-1 as one (n, fnz, fnx) host array

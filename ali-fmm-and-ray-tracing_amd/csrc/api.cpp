@@ -262,6 +262,8 @@ int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   ctx->jobs_all = nullptr;
   ctx->ho_last = nullptr;
   free_ray_bufs(ctx);
+  dfree(ctx->tfm.fmc); dfree(ctx->tfm.w); dfree(ctx->tfm.tab); dfree(ctx->tfm.img);
+  ctx->tfm = alifmm_ctx::TfmBufs();
   for (int b = 0; b < alifmm_ctx::kPinBufs; b++) {
     if (ctx->pin[b]) (void)hipHostFree(ctx->pin[b]);
     if (ctx->pin_ev[b]) (void)hipEventDestroy(ctx->pin_ev[b]);
@@ -300,6 +302,7 @@ int alifmm_set_option(alifmm_ctx* ctx, const char* name, double value) {
     ctx->members = (int)value;
   else if (!strcmp(name, "stripe_log") && (value == 0 || (value >= 3 && value <= 12))) ctx->stripe_log = (int)value;
   else if (!strcmp(name, "xcd_local")) ctx->xcd_local = value != 0;
+  else if (!strcmp(name, "tfm_chunk") && (value == 4 || value == 8 || value == 16 || value == 32)) ctx->tfm_chunk = (int)value;
   else return fail(ctx, ALIFMM_E_ARG, "unknown option or bad value: %s=%g", name, value);
   return ALIFMM_OK;
 }
@@ -336,6 +339,11 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "ray_pack_ms")) *value = ctx->t_ray_pack;
   else if (!strcmp(name, "find_rays_ms")) *value = ctx->t_find_rays;
   else if (!strcmp(name, "take_rays_ms")) *value = ctx->t_take_rays;
+  // last alifmm_tfm call (ms): host -> device copies of the data, the weights and the slot table
+  // (host clock); the delay-and-sum kernel (HIP events)
+  else if (!strcmp(name, "tfm_upload_ms")) *value = ctx->t_tfm_upload;
+  else if (!strcmp(name, "tfm_kernel_ms")) *value = ctx->t_tfm_kernel;
+  else if (!strcmp(name, "tfm_chunk")) *value = ctx->tfm_chunk;
   else return fail(ctx, ALIFMM_E_ARG, "unknown option: %s", name);
   return ALIFMM_OK;
 }
@@ -1607,6 +1615,75 @@ int alifmm_put_field(alifmm_ctx* ctx, int slot, int subgrid, const double* data)
   HIPCHK(hipSetDevice(ctx->device));
   if ((rc = af_ensure_field(ctx, slot, subgrid, fz, fx))) return rc;
   HIPCHK(hipMemcpy(ctx->fields[slot].d, data, (size_t)fz * fx * 8, hipMemcpyHostToDevice));
+  return ALIFMM_OK;
+}
+
+int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+               const float* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+               int niz, int nix, int step, double* image) {
+  if (!ctx) return ALIFMM_E_ARG;
+  if (!ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "tfm: no model");
+  if (!tx_slot || !rx_slot || !fmc || !image) return fail(ctx, ALIFMM_E_ARG, "tfm: null pointer");
+  if (ntx < 1 || nrx < 1 || nt < 2) return fail(ctx, ALIFMM_E_ARG, "tfm: ntx %d, nrx %d, nt %d", ntx, nrx, nt);
+  if (ncomp != 1 && ncomp != 2) return fail(ctx, ALIFMM_E_ARG, "tfm: ncomp %d is not 1 or 2", ncomp);
+  if (!(std::isfinite(fs) && fs > 0) || !std::isfinite(t0)) return fail(ctx, ALIFMM_E_ARG, "tfm: fs %g, t0 %g", fs, t0);
+  if (step < 1 || niz < 1 || nix < 1) return fail(ctx, ALIFMM_E_ARG, "tfm: step %d, window %d x %d", step, niz, nix);
+  // the slots: resident fields of `subgrid`, one shape
+  int fz = 0, fx = 0;
+  std::vector<const double*> tab((size_t)ntx + nrx);
+  for (int k = 0; k < ntx + nrx; k++) {
+    const int s = k < ntx ? tx_slot[k] : rx_slot[k - ntx];
+    if (s < 0 || s >= (int)ctx->fields.size() || !ctx->fields[s].d)
+      return fail(ctx, ALIFMM_E_ARG, "tfm: no field in slot %d", s);
+    const Field& f = ctx->fields[s];
+    if (f.sg != subgrid) return fail(ctx, ALIFMM_E_ARG, "tfm: slot %d holds a subgrid-%d field, not %d", s, f.sg, subgrid);
+    if (k == 0) fz = f.nz, fx = f.nx;
+    if (f.nz != fz || f.nx != fx)
+      return fail(ctx, ALIFMM_E_ARG, "tfm: slot %d is %d x %d, slot %d is %d x %d", s, f.nz, f.nx, tx_slot[0], fz, fx);
+    tab[k] = f.d;
+  }
+  if (iz0 < 0 || ix0 < 0 || (int64_t)iz0 + (int64_t)step * (niz - 1) > fz - 1 ||
+      (int64_t)ix0 + (int64_t)step * (nix - 1) > fx - 1)
+    return fail(ctx, ALIFMM_E_ARG, "tfm: window (%d, %d) + %d x (%d, %d) outside the %d x %d field", iz0, ix0, step, niz,
+                nix, fz, fx);
+  const size_t npair = (size_t)ntx * nrx, ndata = npair * (size_t)nt * ncomp, nimg = (size_t)niz * nix * ncomp;
+  HIPCHK(hipSetDevice(ctx->device));
+  alifmm_ctx::TfmBufs& B = ctx->tfm;
+  HIPCHK(dgrow(&B.fmc, &B.fmc_n, ndata));
+  if (pair_w) HIPCHK(dgrow(&B.w, &B.w_n, npair));
+  HIPCHK(dgrow(&B.tab, &B.tab_n, tab.size()));
+  HIPCHK(dgrow(&B.img, &B.img_n, nimg));
+  const auto c0 = std::chrono::steady_clock::now();
+  HIPCHK(hipMemcpy(B.fmc, fmc, ndata * sizeof(float), hipMemcpyHostToDevice));
+  if (pair_w) HIPCHK(hipMemcpy(B.w, pair_w, npair * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(B.tab, tab.data(), tab.size() * sizeof(double*), hipMemcpyHostToDevice));
+  ctx->t_tfm_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+  af::TfmParams P;
+  P.tx = B.tab;
+  P.rx = B.tab + ntx;
+  P.fmc = B.fmc;
+  P.pair_w = pair_w ? B.w : nullptr;
+  P.image = B.img;
+  P.t0 = t0;
+  P.fs = fs;
+  P.ntx = ntx;
+  P.nrx = nrx;
+  P.nt = nt;
+  P.ncomp = ncomp;
+  P.fnx = fx;
+  P.iz0 = iz0;
+  P.ix0 = ix0;
+  P.niz = niz;
+  P.nix = nix;
+  P.step = step;
+  HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+  HIPCHK(af_launch_tfm(&P, ctx->tfm_chunk, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+  ctx->t_tfm_kernel = ms;
+  HIPCHK(hipMemcpy(image, B.img, nimg * sizeof(double), hipMemcpyDeviceToHost));
   return ALIFMM_OK;
 }
 

@@ -150,6 +150,17 @@ struct alifmm_ctx {
   double t_stream_tail = 0;  // last travel_into: ms from the band kernel's end to the last tile copied
   long stream_fallback = 0;  // last travel_into: fields copied after the kernel (not streamed)
   long exact_redo = 0;       // last travel (subgrid > 1): sources the LDS exact walk handed to the HBM walk
+  // alifmm_tfm: grow-only device buffers (data, pair weights, slot pointer table, image), freed
+  // with the context
+  struct TfmBufs {
+    float* fmc = nullptr;
+    float* w = nullptr;
+    const double** tab = nullptr;
+    double* img = nullptr;
+    size_t fmc_n = 0, w_n = 0, tab_n = 0, img_n = 0;  // capacities in elements
+  } tfm;
+  int tfm_chunk = af::kTfmChunk;  // receivers per register chunk of the TFM kernel (4, 8, 16, 32)
+  double t_tfm_upload = 0, t_tfm_kernel = 0;  // last alifmm_tfm (ms)
 };
 
 // the band width in force for the resident model on the subgrid-sg grid, and the far band's (0: off)
@@ -193,6 +204,17 @@ static inline hipError_t dalloc(T** p, size_t n) {
 }
 static inline void dfree(void* p) {
   if (p) (void)hipFree(p);
+}
+// grow-only device buffer (alifmm_tfm): at least n elements
+template <class T>
+static inline hipError_t dgrow(T** p, size_t* have, size_t n) {
+  if (*p && *have >= n) return hipSuccess;
+  dfree(*p);
+  *p = nullptr;
+  *have = 0;
+  hipError_t e = dalloc(p, n);
+  if (e == hipSuccess) *have = n;
+  return e;
 }
 
 

@@ -2,6 +2,7 @@
 #pragma once
 #include "device_common.h"
 #include "fmm_shared.h"
+#include "tfm_term.h"  // af::TfmParams: the parameter block of the TFM kernel (tfm.hip) and of its host model
 
 namespace af {
 
@@ -174,4 +175,6 @@ hipError_t af_launch_local_ops(const af::LocalOpsParams* P, hipStream_t stream);
 hipError_t af_launch_mat_slowness(const af::DevModel* M, double* out, hipStream_t stream);
 hipError_t af_launch_tbp(const af::DevModel* M, int n, const double* x1, const double* x2, const double* y1,
                          const double* y2, double dnx, int sg, double* out, hipStream_t stream);
+// TFM delay-and-sum (tfm.hip); chunk = receivers per register chunk: 4, 8, 16 or 32
+hipError_t af_launch_tfm(const af::TfmParams* P, int chunk, hipStream_t stream);
 }

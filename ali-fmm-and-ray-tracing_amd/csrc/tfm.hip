@@ -1,0 +1,46 @@
+// tfm.hip — TFM delay-and-sum over resident travel-time fields (include/alifmm.h alifmm_tfm).
+// One thread per pixel; a wave covers 64 consecutive x of one image row (coalesced field reads at
+// step 1), a workgroup kTfmRows rows.  Each thread keeps the delays of RC receivers in registers,
+// walks every transmitter for that chunk (one T_a load per transmitter and chunk) and gathers the
+// two neighbouring samples of each pair's A-scan through L1 / L2; neighbouring pixels have
+// neighbouring delays, so a wave's gathers fall into a few cache lines of that A-scan.  The
+// accumulators stay in registers across chunks; one image store at the end.  Tail tiles, step > 1
+// and nrx not a multiple of RC go through the same code with predicates.  The per-pixel arithmetic
+// and its order are tfm_term.h's (shared with tests/tfm_sim.cpp).
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+
+namespace af {
+
+constexpr int kTfmRows = 4;  // waves (image rows) per workgroup
+
+template <int NC, int RC>
+__global__ __launch_bounds__(64 * kTfmRows) void tfm_kernel(TfmParams P) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  const int i = blockIdx.y * kTfmRows + threadIdx.y;
+  if (i >= P.niz || j >= P.nix) return;
+  double acc[NC];
+  tfm_pixel<NC, RC>(P, tfm_pixel_offset(P, i, j), acc);
+  double* o = P.image + ((int64_t)i * P.nix + j) * NC;
+#pragma unroll
+  for (int c = 0; c < NC; c++) o[c] = acc[c];
+}
+
+template <int NC>
+static hipError_t launch_nc(const TfmParams& P, int chunk, dim3 grid, dim3 block, hipStream_t stream) {
+  if (chunk == 4) hipLaunchKernelGGL((tfm_kernel<NC, 4>), grid, block, 0, stream, P);
+  else if (chunk == 16) hipLaunchKernelGGL((tfm_kernel<NC, 16>), grid, block, 0, stream, P);
+  else if (chunk == 32) hipLaunchKernelGGL((tfm_kernel<NC, 32>), grid, block, 0, stream, P);
+  else hipLaunchKernelGGL((tfm_kernel<NC, kTfmChunk>), grid, block, 0, stream, P);
+  return hipGetLastError();
+}
+
+}  // namespace af
+
+// chunk: receivers per register chunk, 4, 8, 16 or 32 (anything else: kTfmChunk)
+extern "C" hipError_t af_launch_tfm(const af::TfmParams* P, int chunk, hipStream_t stream) {
+  if (P->niz < 1 || P->nix < 1 || (P->ncomp != 1 && P->ncomp != 2)) return hipErrorInvalidValue;
+  const dim3 block(64, af::kTfmRows), grid((P->nix + 63) / 64, (P->niz + af::kTfmRows - 1) / af::kTfmRows);
+  return P->ncomp == 2 ? af::launch_nc<2>(*P, chunk, grid, block, stream) : af::launch_nc<1>(*P, chunk, grid, block, stream);
+}

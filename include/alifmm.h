@@ -165,6 +165,46 @@ int alifmm_init_profile(alifmm_ctx* ctx, int i, int64_t* out16);
  * field computed elsewhere (find_ray's rec_TTF argument, :3105). */
 int alifmm_put_field(alifmm_ctx* ctx, int slot, int subgrid, const double* data);
 
+/* Total-focusing-method (TFM) image of full-matrix-capture data, delay-and-sum over resident
+ * travel-time fields (the first-arrival delay laws): I(p) = sum_a sum_b w_ab s_ab(T_a(p) + T_b(p)).
+ * The fields stay on the device; one image comes back.
+ *   subgrid            the fields' subgrid
+ *   tx_slot[ntx], rx_slot[nrx]  resident slots of the transmitters' / receivers' fields.  Every
+ *                      named slot holds a field of `subgrid` and of one common shape (fnz, fnx);
+ *                      slots may repeat, the lists may overlap or be the same array
+ *   fmc                float32 [ntx][nrx][nt][ncomp]; ncomp 1: real RF, 2: analytic signal, re and
+ *                      im interleaved
+ *   t0, fs             time [s] of sample 0, sampling rate [Hz]
+ *   pair_w (nullable)  float32 [ntx][nrx] (apodisation, or a trans_pairs-style 0/1 mask)
+ *   iz0, ix0, niz, nix, step  pixel window on the fields' fine grid: pixel (i, j) is node
+ *                      (iz0 + step i, ix0 + step j).  Pixels are field nodes: no spatial
+ *                      interpolation of T is defined or needed
+ *   image              float64 [niz][nix][ncomp]
+ * One term (a, b) at pixel p, all in float64, operations in this order, no contraction:
+ *   1. w = pair_w ? (double)pair_w[a][b] : 1.0; if w == 0 the term is 0
+ *   2. u = ((T_a(p) + T_b(p)) - t0) * fs
+ *   3. the term is 0 unless u >= 0 && u < nt - 1 (written so that NaN, +-inf and huge values fail
+ *      it; made before any conversion to an integer)
+ *   4. k = (int64)u, f = u - (double)k
+ *   5. x0 = (double)fmc[a][b][k], x1 = (double)fmc[a][b][k+1], per component
+ *   6. term = w * (x0 + f * (x1 - x0))
+ * I(p) = the float64 sum of the terms in an order that is fixed per pixel (it depends on ntx, nrx
+ * and option "tfm_chunk" only, not on the window, the step or the pixel's place in a tile): the
+ * same pixel computed through two windows has the same bits.
+ * ALIFMM_E_ARG with a message, the context staying usable, when: the context has no model; a slot
+ * is empty; the slots mix subgrids or shapes; ntx or nrx < 1 or nt < 2; ncomp is not 1 or 2; fs
+ * is not finite and positive or t0 is not finite; step, niz or nix < 1; the window reaches outside
+ * the field; tx_slot, rx_slot, fmc or image is NULL.
+ * The fields in the slots are not modified.  All offsets into fmc are 64-bit (ntx nrx nt ncomp
+ * passes 2^31 at realistic sizes).  The data, the weights, the slot pointer table and the image
+ * live in grow-only device buffers of the context, freed with it.  alifmm_get_option:
+ * "tfm_upload_ms" (host -> device copies) and "tfm_kernel_ms" (the kernel) of the last call;
+ * alifmm_set_option "tfm_chunk" (4, 8, 16 or 32, default 8): receivers whose delays a pixel keeps
+ * in registers per pass over the transmitters (changes the summation order, so the last bits). */
+int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+               const float* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+               int niz, int nix, int step, double* image);
+
 /* n straight-segment times on the resident model (time_between_points() :2835-2989; the
  * coordinates are fine-grid indices of `subgrid`).  ray_time() (:2992-3022) = ordered sum. */
 int alifmm_time_between_points(alifmm_ctx* ctx, int n, const double* x1, const double* x2, const double* y1,
