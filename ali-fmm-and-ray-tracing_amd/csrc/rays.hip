@@ -465,10 +465,16 @@ __global__ __launch_bounds__(64 * kRayWaves) __attribute__((amdgpu_waves_per_eu(
   // time_between_points() of consecutive points, read back from the ray buffer) and lane order
   // gives the reference's left-to-right sum, so the per-step walk carries no serial segment time
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent");  // lane 0's point stores, visible to the group
+  // A ray cut short (point capacity, empty plane) has no time (0): the reference raises there and
+  // never calls ray_time on such a ray, and its points need not be ones time_between_points() can
+  // walk.  A horizontal segment at z = k + 0.5 with k odd has next_y == end_y at the start, the
+  // reference's strict '<' never sets fin_y, and the walk runs off the grid without end; rays that
+  // circle on a flat field until the capacity hold such segments.
+  const bool timed = !(flags & 6);
 #ifdef AF_RAY_DIAG_NOTIME  // diagnostic build only (no ray times): the walk alone
   for (long k0 = 0; k0 < 0; k0 += G) {
 #else
-  for (long k0 = 0; k0 < npts - 1; k0 += G) {
+  for (long k0 = 0; timed && k0 < npts - 1; k0 += G) {
 #endif
     const long k = k0 + lane;
     const bool ok = k < npts - 1;

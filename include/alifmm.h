@@ -121,7 +121,8 @@ int alifmm_copy_fields(alifmm_ctx* ctx, int first_slot, int n, double* dst, int 
 /* Trace npairs rays (replaces find_ray() :3104-3465 incl. ray_time() :2992-3022).
  *   field_slot[k]        resident field of the RECEIVER of ray k (its subgrid is used)
  *   src_xy[2k], rec_xy[2k]  source / receiver (x, z) on that field's fine grid
- *   times[k]             ray travel time [s]
+ *   times[k]             ray travel time [s]; 0 for a ray cut short (flags bit1 or bit2), which the
+ *                        reference never times
  *   ray_len[k]           number of points (>= 2)
  *   flags[k]             bit0: reference's early exit ("Travel time to receiver increasing"),
  *                        bit1: point capacity reached, bit2: empty candidate plane

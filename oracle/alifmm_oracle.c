@@ -1200,10 +1200,11 @@ static double tbp_impl(double x1, double x2, double y1, double y2, double dnx, l
     return section_time;
 }
 
-/* find_ray :3104-3465.  Returns number of points (>=2) or <0 on error. */
+/* find_ray :3104-3465.  Returns number of points (>=2) or <0 on error (-3: point capacity, -4: empty
+ * plane); *walked (may be NULL): the points written to rx / ry before a negative return. */
 static long find_ray_impl(double dnx, const table_t *vd, double srcx, double srcy, double recx, double recy,
                           const double *ttf, long fnz, long fnx, const mat_t *m, long sg, double *rx, double *ry,
-                          long max_pts, double *time_out, int *early) {
+                          long max_pts, double *time_out, int *early, long *walked) {
     long plane_dist = 3;
     long sd = plane_dist * sg + 1;
     long sd2 = (plane_dist - 1) * sg + 1;
@@ -1217,13 +1218,14 @@ static long find_ray_impl(double dnx, const table_t *vd, double srcx, double src
     long nnz = fnx; /*                   nnz = rec_TTF.shape[1] (cols) */
     double *TT = (double *)malloc(sizeof(double) * (size_t)(2 * sd + 8 + 2 * sd2 + 8));
     *early = 0;
+    if (walked) *walked = 0;
 #define RT(r, c) ttf[(long)(r) * fnx + (long)(c)]
     while ((last_x - recx) * (last_x - recx) + (last_y - recy) * (last_y - recy) > (1.6 * sg) * (1.6 * sg)) {
         if ((last_x - recx) * (last_x - recx) + (last_y - recy) * (last_y - recy) < (double)(4 * sg) * (4 * sg)) {
             lvx = recx - last_x;
             lvy = recy - last_y;
         }
-        if (ray_len + 1 >= cap) { free(TT); return -3; }
+        if (ray_len + 1 >= cap) { free(TT); if (walked) *walked = ray_len; return -3; }
         double cand[4] = {fabs(lvx), fabs(lvx + lvy) / sqrt(2.0), fabs(lvy), fabs(lvx - lvy) / sqrt(2.0)};
         int dir = 0;
         for (int q = 1; q < 4; q++) if (cand[q] > cand[dir]) dir = q;
@@ -1284,7 +1286,7 @@ static long find_ray_impl(double dnx, const table_t *vd, double srcx, double src
                 TT[i] = RT(yc, xc) + tbp_impl(last_x, (double)xc, last_y, (double)yc, dnx, sg, vd, m);
             }
         }
-        if (n <= 0) { free(TT); return -4; } /* SURVEY B-D11: empty candidate set */
+        if (n <= 0) { free(TT); if (walked) *walked = ray_len; return -4; } /* SURVEY B-D11: empty candidate set */
         double minimum, min_i;
         if (TT[0] < TT[n - 1]) { minimum = TT[0]; min_i = 0; }
         else { minimum = TT[n - 1]; min_i = (double)(n - 1); }
@@ -1392,7 +1394,22 @@ long oref_find_ray(double dnx, const double *vd, int ncol, double srcx, double s
     base_t b;
     if (make_base(&b, nnz, nnx, veln, velpn, vel_map, stif)) return -1;
     table_t t = {vd, ncol};
-    long r = find_ray_impl(dnx, &t, srcx, srcy, recx, recy, ttf, fnz, fnx, &b.m, sg, rx, ry, max_pts, time_out, early);
+    long r = find_ray_impl(dnx, &t, srcx, srcy, recx, recy, ttf, fnz, fnx, &b.m, sg, rx, ry, max_pts, time_out, early,
+                           NULL);
+    free_base(&b);
+    return r;
+}
+
+/* oref_find_ray with the walk's length on a negative return: rx / ry hold *walked points then. */
+long oref_find_ray_walked(double dnx, const double *vd, int ncol, double srcx, double srcy, double recx, double recy,
+                          const double *ttf, int fnz, int fnx, int nnz, int nnx, const double *veln,
+                          const int64_t *velpn, const double *vel_map, const int64_t *stif, int sg, double *rx,
+                          double *ry, long max_pts, double *time_out, int *early, long *walked) {
+    base_t b;
+    if (make_base(&b, nnz, nnx, veln, velpn, vel_map, stif)) return -1;
+    table_t t = {vd, ncol};
+    long r = find_ray_impl(dnx, &t, srcx, srcy, recx, recy, ttf, fnz, fnx, &b.m, sg, rx, ry, max_pts, time_out, early,
+                           walked);
     free_base(&b);
     return r;
 }

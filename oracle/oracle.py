@@ -14,7 +14,12 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ALIFMM_ORACLE_LIB: another build of the same restatement (lib/liboracle_cr.so, the CR-trig one)
 _LIB_PATH = os.environ.get("ALIFMM_ORACLE_LIB") or os.path.join(_HERE, "lib", "liboracle.so")
+# the two builds of the restatement by name, for open_lib(): glibc trig (golden-pinned) and the
+# device's correctly rounded trig
+LIB_GLIBC = os.path.join(_HERE, "lib", "liboracle.so")
+LIB_CR = os.path.join(_HERE, "lib", "liboracle_cr.so")
 _lib = None
+_libs = {}
 
 _d = ctypes.c_double
 _i = ctypes.c_int
@@ -26,12 +31,15 @@ def build():
     subprocess.check_call(["make", "-s", "-C", _HERE])
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_LIB_PATH):
+def open_lib(path):
+    """A build of the restatement by its path (LIB_GLIBC, LIB_CR), loaded once per process: several
+    builds can be used side by side by passing the result as `lib=` to time_between_points and
+    find_ray_walked.  lib() stays the default one (ALIFMM_ORACLE_LIB, else LIB_GLIBC)."""
+    path = os.path.abspath(path)
+    if path not in _libs:
+        if not os.path.exists(path):
             build()
-        L = ctypes.CDLL(_LIB_PATH)
+        L = ctypes.CDLL(path)
         L.oref_travel.restype = _i
         L.oref_travel.argtypes = [_d, _d, _i, _i, _p, _p, _p, _p, _p, _p, _i, _d, _d, _d, _d, _p]
         L.oref_travel_finer_grid.restype = _i
@@ -49,7 +57,16 @@ def lib():
         L.oref_fouds18.argtypes = [_i, _i, _p, _p, _i, _i, _d, _d, _p, _p, _p, _p, _p, _i]
         L.oref_group_vel.restype = _d
         L.oref_group_vel.argtypes = [_d, _l, _l, _l, _l, _l, _d]
-        _lib = L
+        L.oref_find_ray_walked.restype = _l
+        L.oref_find_ray_walked.argtypes = L.oref_find_ray.argtypes + [_p]
+        _libs[path] = L
+    return _libs[path]
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        _lib = open_lib(_LIB_PATH)
     return _lib
 
 
@@ -125,10 +142,12 @@ def travel_batch(scx, scz, veln, velpn, vel_map, stif_den, avlist2, phase_vel, s
     return out
 
 
-def time_between_points(x1, x2, y1, y2, dnx, subgrid_size, velocity_dat, veln, velpn, vel_map, stif_den):
-    """time_between_points() Anis_TTF_rays.py:2835-2989."""
-    m = _Model(veln, velpn, vel_map, stif_den, velocity_dat, velocity_dat)
-    return lib().oref_time_between_points(float(x1), float(x2), float(y1), float(y2), dnx, int(subgrid_size),
+def time_between_points(x1, x2, y1, y2, dnx, subgrid_size, velocity_dat, veln, velpn, vel_map, stif_den, lib=None):
+    """time_between_points() Anis_TTF_rays.py:2835-2989.  lib: a build from open_lib() (default: lib())."""
+    m = velocity_dat if isinstance(velocity_dat, _Model) else _Model(veln, velpn, vel_map, stif_den, velocity_dat,
+                                                                     velocity_dat)
+    L = lib if lib is not None else globals()["lib"]()
+    return L.oref_time_between_points(float(x1), float(x2), float(y1), float(y2), dnx, int(subgrid_size),
                                           _ptr(m.av), m.ncol, m.nnz, m.nnx, _ptr(m.veln), _ptr(m.velpn),
                                           _ptr(m.vel_map), _ptr(m.stif))
 
@@ -149,6 +168,38 @@ def find_ray(dnx, velocity_dat, source, receiver, rec_TTF, veln, velpn, vel_map,
     if n < 0:
         raise RuntimeError("oracle find_ray failed rc=%d" % n)
     return rx[:n].copy(), ry[:n].copy(), t.value
+
+
+def model(velocity_dat, veln, velpn, vel_map, stif_den):
+    """The model arrays converted once, for many time_between_points / find_ray_walked calls on one
+    model (pass it as `velocity_dat`; the other model arguments are then ignored)."""
+    return _Model(veln, velpn, vel_map, stif_den, velocity_dat, velocity_dat)
+
+
+def find_ray_walked(dnx, velocity_dat, source, receiver, rec_TTF, veln, velpn, vel_map, stif_den, subgrid_size,
+                    cap=None, lib=None):
+    """find_ray() with everything it returns -> (rc, early, ray_x, ray_y, time, walked).
+    rc: the point count, or -3 (the point capacity 5 (nnz + nnx), or `cap` if smaller) or -4 (an
+    empty search plane); early: the "travel time to receiver increasing" exit; ray_x / ray_y: the rc
+    points, or on a negative rc the `walked` points written before it (time is then 0.0).
+    lib: a build from open_lib() (default: lib())."""
+    m = velocity_dat if isinstance(velocity_dat, _Model) else _Model(veln, velpn, vel_map, stif_den, velocity_dat,
+                                                                     velocity_dat)
+    L = lib if lib is not None else globals()["lib"]()
+    ttf = _f64(rec_TTF)
+    full = 5 * (m.nnz + m.nnx)
+    cap = full if cap is None else int(cap)
+    rx = np.zeros(max(cap, 2))
+    ry = np.zeros(max(cap, 2))
+    t = ctypes.c_double(0.0)
+    early = ctypes.c_int(0)
+    walked = ctypes.c_long(0)
+    n = L.oref_find_ray_walked(dnx, _ptr(m.av), m.ncol, float(source[0]), float(source[1]), float(receiver[0]),
+                               float(receiver[1]), _ptr(ttf), ttf.shape[0], ttf.shape[1], m.nnz, m.nnx, _ptr(m.veln),
+                               _ptr(m.velpn), _ptr(m.vel_map), _ptr(m.stif), int(subgrid_size), _ptr(rx), _ptr(ry),
+                               cap, ctypes.byref(t), ctypes.byref(early), ctypes.byref(walked))
+    k = n if n >= 0 else walked.value
+    return int(n), int(early.value), rx[:k].copy(), ry[:k].copy(), t.value if n >= 0 else 0.0, int(k)
 
 
 def update(veln, velpn, vel_map, nsts, ttn, iz, ix, dnx, nnz, nnx, phase_vel, stif_den):

@@ -229,3 +229,112 @@ def test_band_case_matrix_preconditions():
         assert np.array_equal(BC.model_field(BC.ORIGIN_CASE, s), BC.model_field(BC.ORIGIN_ZERO, s)), s
     dz = [c for c in BC.PARAM_CASES if c.dnz != c.dnx]
     assert len(dz) == 1 and dz[0].dnz == 1.5e-3 and dz[0].dnx == 1e-3
+
+
+def test_ray_case_matrix_preconditions():
+    """What tests/test_gpu_rays_small.py relies on, from the oracle alone (tests/ray_cases.py).
+    Every segment case is a 2-point ray on its pit field whose time is bit-equal to the same
+    build's time_between_points; the piece and run classes are what the case names say and cover
+    the ray kernel's edges (8 / 9 and 12 / 13 pieces, 4 / 5 runs, a run starting at piece 7, 8, 11,
+    12 and 256, A B A, every record of the 256-record model); the models lie in the material
+    classes they are named for; the walk cases have the lengths, flags and return codes their table
+    states; and every case agrees between the glibc build and the correctly rounded one (lengths,
+    flags and return codes equal, points within 1e-9, times within 1e-12), with no exception."""
+    import ray_cases as RC
+
+    builds = (O.LIB_GLIBC, O.LIB_CR)
+
+    def agree(b):
+        g, c = (RC.batch_reference(b, p) for p in builds)
+        assert len(g) == len(c) == len(b.rays)
+        for k, (a, d) in enumerate(zip(g, c)):
+            assert (a.rc, a.early, a.walked) == (d.rc, d.early, d.walked), (b.name, k, a, d)
+            assert len(a.x) == len(d.x) == a.walked and (a.rc < 0 or a.rc == a.walked), (b.name, k)
+            assert np.max(np.abs(a.x - d.x)) <= 1e-9 and np.max(np.abs(a.y - d.y)) <= 1e-9, (b.name, k)
+            assert abs(a.t - d.t) <= 1e-12 * abs(a.t), (b.name, k, a.t, d.t)
+        return g
+
+    # the models: record counts, and which of them the ray kernel keeps in LDS
+    for name, (count, lds) in RC.SEG_MODELS.items():
+        m = RC.model(name, *RC.SEG_H)
+        n = RC.record_count(m)
+        assert (100 < n <= 256) if count is None else n == count, (name, n)
+        assert lds == (n <= 256 and RC.stiffness_rows(m) <= 64 and 361 * m.table.shape[1] <= 722), name
+    assert sorted(set(RC.model("vt3", *RC.SEG_H).velpn.ravel())) == [0, 1, 2]
+    assert RC.stiffness_rows(RC.model("stif65", *RC.SEG_H)) == 65
+    assert np.array_equal(RC.model("stripes", *RC.SEG_V).ids, RC.model("stripes", *RC.SEG_H).ids.T)
+
+    # the segments
+    nseg = 0
+    for mname, shape in RC.SEGMENT_RUNS:
+        m = RC.model(mname, *shape)
+        for sg in RC.SEG_SUBGRIDS:
+            segs = RC.segments(shape, sg)
+            keep, rsegs = RC.ray_segments(shape, sg)
+            b = RC.segment_batch(mname, shape, sg)
+            assert len(b.rays) == len(rsegs) and len(b.fields) <= 64
+            agree(b)
+            tg, tc = (RC.segment_times(mname, shape, sg, p) for p in builds)
+            assert np.all(np.abs(tg - tc) <= 1e-12 * np.abs(tg)), (mname, shape, sg)
+            for p, t in zip(builds, (tg, tc)):
+                for k, s, r in zip(keep, rsegs, RC.batch_reference(b, p)):
+                    assert r.rc == 2 and r.t == t[k], (mname, shape, sg, s.name, r.rc, r.t, t[k])
+                    assert (r.x[0], r.y[0], r.x[1], r.y[1]) == (s.x1, s.y1, s.x2, s.y2), s.name
+            for s in segs:
+                assert abs(s.x1 - round(s.x1)) <= 0.4 and abs(s.y1 - round(s.y1)) <= 0.4, s.name  # off .5
+                pieces, runs, starts, recs = RC.seg_classes(m, s, sg)
+                if s.pieces is not None:
+                    assert pieces == s.pieces, (mname, sg, s.name, pieces)
+                if s.runs is not None and mname in ("stripes", "vt3"):
+                    assert runs == s.runs, (mname, sg, s.name, runs)
+                assert runs == 1 or mname != "iso"
+            nseg += len(segs)
+    assert nseg >= 4000  # 7 models x 2 subgrids x 272 segments on SEG_H, 2 x 2 x 95 on SEG_V
+    for shape in (RC.SEG_H, RC.SEG_V):
+        m = RC.model("stripes", *shape)
+        for sg in RC.SEG_SUBGRIDS:
+            segs = RC.segments(shape, sg)
+            cl = [RC.seg_classes(m, s, sg) for s in segs if s.pieces is not None]
+            assert {8, 9, 12, 13, 255, 256, 257} <= {c[0] for c in cl}
+            assert {1, 2, 4, 5, 9, 10} <= {c[1] for c in cl}
+            assert {7, 8, 11, 12, 256} <= {k for c in cl for k in c[2]}
+            assert any(c[0] == 12 and c[2] == [11] for c in cl) and any(c[0] == 13 and c[2] == [12] for c in cl)
+            assert any(c[3] == [1, 0, 1] for c in cl)  # A B A
+            assert sum(s.pieces is None for s in segs) >= (200 if shape == RC.SEG_H else 24)
+            assert sum(1 for s in segs if s.x1 == s.x2 and s.y1 == s.y2) >= 1
+    m = RC.model("m256", *RC.SEG_H)
+    seen = set()
+    for s in RC.segments(RC.SEG_H, 1):
+        seen.update(RC.seg_classes(m, s, 1)[3])
+    assert len(seen) == 256  # whichever record the library numbers 255 lies on a tested segment
+
+    # the walks: both builds agree; lengths from 2 points up; the thin grids' rays all complete
+    for b in RC.WALK_BATCHES:
+        g = agree(b)
+        lens = [r.rc for r in g]
+        assert min(lens) == 2 and max(lens) >= (25 if min(b.nz, b.nx) <= 3 else 55), (b.name, max(lens))
+        assert b.sg > 3 or all(r.early == 0 for r in g) or min(b.nz, b.nx) <= 3, b.name
+    assert all(max(r.rc for r in agree(b)) >= 70 for b in RC.DIST_BATCHES)
+    g = agree(RC.DIAG_TIE_BATCH)
+    assert all(r.rc >= 2 and r.early == 1 for r in g) and any(r.rc > 2 for r in g)
+    # one case per exit of the walk (the table of the matrix)
+    for b in RC.EXIT_BATCHES:
+        g = dict(zip(RC.EXIT_NAMES, agree(b)))
+        assert (g["early"].rc, g["early"].early) == (72, 1), b.name
+        assert (g["leaves_grid"].rc, g["leaves_grid"].early) == (48, 0), b.name
+        e = g["empty_plane"]
+        assert (e.rc, e.early) == ((-4, 0) if b.sg >= 3 else (47, 0)) and e.walked >= 40, (b.name, e.rc, e.walked)
+        for k in ("not_entered_same", "not_entered_1.5"):
+            assert (g[k].rc, g[k].early) == (2, 0), (b.name, k)
+        assert g["near_1.6"].rc == 2 and g["on_1.6"].rc == 2
+    # the capacity ray and the list it is permuted in: lengths from 2 to the capacity
+    g = agree(RC.MIX_BATCH)
+    cap = g[RC.CAP_RAY]
+    assert (cap.rc, cap.walked) == (-3, RC.CAP_POINTS - 1)
+    # the orbit holds segments time_between_points() cannot walk (ray_cases.walk_cells): the reference
+    # never times a ray cut short, and the device must not either
+    endless = [k for k in range(cap.walked - 1)
+               if RC.walk_cells(cap.x[k], cap.x[k + 1], cap.y[k], cap.y[k + 1], 1, limit=1000) is None]
+    assert endless and all(cap.y[k] == cap.y[k + 1] and cap.y[k] % 2 == 1.5 for k in endless), endless[:5]
+    assert min(r.walked for r in g) == 2 and sum(r.early for r in g) >= 1
+    assert sum(1 for r in g if r.rc == 2) >= 2 and sum(1 for r in g if r.rc > 20) >= 8
