@@ -620,12 +620,12 @@ int af_ensure_field(alifmm_ctx* ctx, int slot, int sg, int fz, int fx, long extr
 }
 
 // members per source of the band kernel: the largest K <= kMaxK whose grid (nsrc padded to 8, times
-// K workgroups, af_band_wgs_per_cu() of them per CU) is co-resident, with >= 2 stripes per member
+// K workgroups, one per CU) is co-resident, with >= 2 stripes per member
 // (option "members" forces a value, still capped by residency and by the stripe count: a member
 // without a stripe would only take its 1 / K share of the work lists, travel_chunk capL / K, from
 // the members that own cells)
 static int choose_members(const alifmm_ctx* ctx, int n, int fx) {
-  const int by_cu = std::max(1, ctx->n_cu * af_band_wgs_per_cu() / (8 * ((n + 7) / 8)));
+  const int by_cu = std::max(1, ctx->n_cu / (8 * ((n + 7) / 8)));
   if (ctx->members > 0) {
     int K = std::max(1, std::min(ctx->members, by_cu));
     // the stripe width follows K (travel_chunk) unless "stripe_log" fixes it: lower K until it fits

@@ -39,7 +39,7 @@
 // every wave before the flag, and read with sc1 loads after the flag (MI355X_MICROARCH.md
 // "inter-workgroup visibility", Valid forms); once every member has reported the same XCD
 // (HW_REG_XCC_ID in its exchange word) the stores are plain and complete in that XCD's L2, where
-// the sc1 loads are served (AF_XCD_LOCAL).  Flags and rim lists are double-buffered by parity.
+// the sc1 loads are served (xst below).  Flags and rim lists are double-buffered by parity.
 #define CR_LDS_TABLES  // cr_math.h tables in LDS (crm::lds_init at kernel start)
 #include <algorithm>
 #include <type_traits>
@@ -52,138 +52,29 @@
 namespace af {
 namespace kb {
 
-// Workgroups per CU (AF_WG_PER_CU): 1 = one 768-thread member per CU with the whole LDS; 2 = two
-// 384-thread members per CU (of any sources), each with half the LDS, so that one member's
-// barrier waits and memory round trips are covered by the other's work (the host then runs
-// twice the members per source, choose_members / af_band_wgs_per_cu).
-#ifndef AF_WG_PER_CU
-#define AF_WG_PER_CU 1
-#endif
-// 768 threads: 12 waves, 3 per SIMD (the kernel fits 168 VGPRs): the claim and accept passes
-// hide more latency (C4 128 sources: 456 -> 437 ms with 512 -> 768, tools/kbench.py).  Several
-// members per CU need workgroups the wave placement can pack: at 3 waves per SIMD two 384-thread
-// workgroups (2 + 2 + 1 + 1 waves each) do not fit together (measured: the second wave of
-// workgroups waits for the first, tools/micro/residency.hip), three 256-thread ones (one wave per
-// SIMD each) do.
-#ifndef AF_THREADS
-#define AF_THREADS (768 / AF_WG_PER_CU)
-#endif
-constexpr int kThreads = AF_THREADS;
+// One 768-thread member per CU with the whole LDS: 12 waves, 3 per SIMD (the kernel fits 168
+// VGPRs), so the claim and accept passes hide more latency (C4 128 sources: 456 -> 437 ms with
+// 512 -> 768, tools/kbench.py).  Several smaller members per CU were not kept.
+constexpr int kThreads = 768;
 constexpr int kWaves = kThreads / 64;
 // LDS heads of the lists (longer lists spill to the global arrays, HList): sized to the LDS left
 // (157 KB of 160), the close set to the C4 peak (3 295 live slots of one member at K = 2): 2560 / 1536
 // -> 3328 / 1792 took the C4 band from 416 to 405 ms, the accepted list 1024 -> 1536 (the claim
 // then stays in LDS and tile-sorted in the widest steps) to 388 ms; 161 KB of LDS in all
-// (two members per CU: half of it each, 77.7 KB)
-#if AF_WG_PER_CU == 3
-#define AF_LCAP_D 960
-#define AF_ECAP_D 512
-#define AF_ACAP_D 384
-#define AF_HASHLOG_D 11
-#define AF_SORTB_D 128
-#elif AF_WG_PER_CU == 2
-#define AF_LCAP_D 1664
-#define AF_ECAP_D 896
-#define AF_ACAP_D 768
-#define AF_HASHLOG_D 11
-#define AF_SORTB_D 256
-#else
-#define AF_LCAP_D 3328
-#define AF_ECAP_D 1792
-#define AF_ACAP_D 1536
-#define AF_HASHLOG_D 13
-#define AF_SORTB_D 512
-#endif
-#ifndef AF_LCAP
-#define AF_LCAP AF_LCAP_D
-#endif
-#ifndef AF_ECAP
-#define AF_ECAP AF_ECAP_D
-#endif
-#ifndef AF_ACAP
-#define AF_ACAP AF_ACAP_D
-#endif
-constexpr int kLcap = AF_LCAP, kAcap = AF_ACAP, kEcap = AF_ECAP;
-constexpr int kBcap = 512 / AF_WG_PER_CU, kDcap = 256 / AF_WG_PER_CU, kRcap = 1024 / AF_WG_PER_CU;
-#ifndef AF_X1_SLEEP
-#define AF_X1_SLEEP 1
-#endif
-// claim items per lane and pass (the ownership claim; 1, 4 and 6 measured slower)
-#ifndef AF_CLAIM_OWN_U
-#define AF_CLAIM_OWN_U 2
-#endif
-constexpr int kCU = AF_CLAIM_OWN_U;
-// the boundary list read in place after the interior one (1) or copied behind it (0)
-#ifndef AF_BL_INPLACE
-#define AF_BL_INPLACE 1
-#endif
-#ifndef AF_CLAIM_ADAPT
-#define AF_CLAIM_ADAPT 1
-#endif
-#ifndef AF_FB_ROUND
-#define AF_FB_ROUND (128 >> (13 - AF_HASHLOG_D))
-#endif
-#ifndef AF_DIAG_DBL
-#define AF_DIAG_DBL 0
-#endif
-#ifndef AF_PROF_SPILL
-#define AF_PROF_SPILL 0
-#endif
-#ifndef AF_PROF_CLAIM  // diagnostic: sub[2] = the accepted list's tile sort, sub[3] = the claim's closing drain
-#define AF_PROF_CLAIM 0
-#endif
-#ifndef AF_PROF_FBWAIT
-#define AF_PROF_FBWAIT 0
-#endif
-// diagnostic: sub[2] / sub[3] = evaluation time (from the phase start) of the slowest wave with
-// interior cells only / with a boundary cell, summed over the steps with both (sub[1]: their count,
-// sub[0]: XCD-local steps, x 100)
-#ifndef AF_PROF_EVW
-#define AF_PROF_EVW 0
-#endif
-// diagnostic: sub[2] / sub[3] = (1) the close-set scan / the scan + the drain before the X1
-// barrier, from the step's start; (2) P0 / P0 + the accept scan, from the X1 barrier
-#ifndef AF_PROF_SEG
-#define AF_PROF_SEG 0
-#endif
-// fallback fouds18_A(): four lanes per cell (1) or one (0)
-#ifndef AF_F18_SPLIT
-#define AF_F18_SPLIT 1
-#endif
-// evaluate: boundary cells in the first pass (1) or last (0: measured faster, 416 vs 422 ms)
-#ifndef AF_EVAL_BFIRST
-#define AF_EVAL_BFIRST 0
-#endif
+constexpr int kLcap = 3328, kAcap = 1536, kEcap = 1792;
+constexpr int kBcap = 512, kDcap = 256, kRcap = 1024;
+constexpr int kCU = 2;  // claim items per lane and pass (the ownership claim; 1, 4 and 6 measured slower)
 // accepted list ordered by 8x8 tile (counting sort over kSortB buckets) before the claim, when it
-// has more than AF_SORT_ACC entries (0: never): the claim's status loads and, through the claim
-// order, the evaluation's stencil loads of one wavefront then touch few cache lines
-#ifndef AF_SORT_ACC
-#define AF_SORT_ACC 256
-#endif
-// ... and only with at most AF_SORT_KMAX members per source (narrow stripes gain nothing from it)
-#ifndef AF_SORT_KMAX
-#define AF_SORT_KMAX 8
-#endif
-#ifndef AF_SORTB
-#define AF_SORTB AF_SORTB_D
-#endif
-#ifndef AF_NB_MIX
-#define AF_NB_MIX 2
-#endif
-constexpr int kSortB = AF_SORTB;
+// has more than kSortAcc entries: the claim's status loads and, through the claim order, the
+// evaluation's stencil loads of one wavefront then touch few cache lines
+constexpr int kSortAcc = 256;
+// ... and only with at most kSortKmax members per source (narrow stripes gain nothing from it)
+constexpr int kSortKmax = 8;
+constexpr int kSortB = 512;
 AF_DEV int tile_bucket(int c) { return ((pkz(c) >> 3) & (kSortB / 32 - 1)) << 5 | ((pkx(c) >> 3) & 31); }
-#ifndef AF_ACC_U
-#define AF_ACC_U 1
-#endif
-constexpr int kAccU = AF_ACC_U;  // close-set entries per lane per accept pass (2 and 4 measured slower)
+constexpr int kAccU = 1;  // close-set entries per lane per accept pass (2 and 4 measured slower)
 // model tables staged in LDS (more materials / stiffness rows: the model arrays are read instead)
-#ifndef AF_MATLDS
-#define AF_MATLDS (256 / AF_WG_PER_CU)
-#endif
-#ifndef AF_STABLDS
-#define AF_STABLDS 64
-#endif
-constexpr int kStabLds = AF_STABLDS, kPtabLds = 722, kMatLds = AF_MATLDS;
+constexpr int kStabLds = 64, kPtabLds = 722, kMatLds = 256;
 constexpr int kDirty = (int)0x80000000u;  // close-set slot: committed last step (edge cell)
 constexpr int kCell = 0x7fffffff;
 
@@ -191,16 +82,11 @@ constexpr int kCell = 0x7fffffff;
 // the flush at the end), own tiles per member with an LDS counter
 constexpr int kTdCap = ts::kListCap;
 constexpr int kTileMax = ts::kOwnTileMax;
-// AF_HS_VEC: 16-byte system-scope stores (1) or 8-byte (0)
-#ifndef AF_HS_VEC
-#define AF_HS_VEC 1
-#endif
-#ifndef AF_HS_U
-#define AF_HS_U 4  // items per thread and batch of stage_tiles
-#endif
+constexpr int kHsU = 4;  // items per thread and batch of stage_tiles
 
-// LDS of the fallback's staging windows (kFbRound x 25 doubles)
-constexpr int kHashArr = AF_FB_ROUND * 25 * 2;
+// cells per staging round of the fallback, and the LDS of its staging windows (kFbRound x 25 doubles)
+constexpr int kFbRound = 128;
+constexpr int kHashArr = kFbRound * 25 * 2;
 
 struct Lds {
   double red[kWaves];
@@ -220,11 +106,9 @@ struct Lds {
   double Dv[2][kDcap];  // ... and their T
   int Rx[kRcap];  // claim items from the neighbour members' accepted rim cells; fallback list
   alignas(16) int H[kHashArr];  // fallback staging windows
-#if AF_SORT_ACC
   int As[kAcap];     // the accepted list in tile order
   int Sb[kSortB];    // bucket counts -> offsets
   int Sw[kWaves];    // per-wave bucket sums of the scan
-#endif
   // host streaming (BandParams::hs): known-cell counters of the own tiles (two 16-bit counters per
   // word; 0xffff once published), this step's completed tiles (own tile indices)
   unsigned tcnt[kTileMax / 2];
@@ -238,58 +122,25 @@ struct Lds {
   unsigned long long nE2;  // claimed-list lengths: interior (low half), boundary (high half)
   int nA, nF, hi, nRx, live_g, err_g, err, nFb;
   int nDb[2];  // [step parity]: lengths of Dc / Dv
-  int xl;  // AF_XCD_LOCAL: every member of the source on this member's XCD (set by the exchange)
+  int xl;  // every member of the source on this member's XCD (set by the exchange)
   int takenb[2], nRb[2];  // [step parity]: fresh close-set slots taken by the commit; rim-list length
   int nrim[2];  // rim-list lengths of the neighbour members (left, right) this step
-#if AF_PROF_EVW
-  long long evt[kWaves];  // diagnostic: each wave's evaluation end
-  int evb[kWaves];        // ... and whether it had cells (1) with a boundary one (2)
-#endif
 };
 
 
 // The band kernel's working field Tb (per source, in the arena; its two edge buffers follow it):
-// AF_BRICK = 1 stores 4 x 4 bricks of doubles, one 128-byte line each, so the 12-point stencils
-// of a wavefront's cells touch fewer lines whatever the direction of the front (modelled on the
-// C4 front in the kernel's claim order: 0.87 instead of 1.26 lines per evaluated cell); 0 is
-// row-major.  Each member writes the row-major result of its stripes at the end (copy_out_own).
-#ifndef AF_BRICK
-#define AF_BRICK 1
-#endif
+// 4 x 4 bricks of doubles, one 128-byte line each, so the 12-point stencils of a wavefront's
+// cells touch fewer lines whatever the direction of the front (modelled on the C4 front in the
+// kernel's claim order: 0.87 instead of 1.26 lines per evaluated cell of a row-major field).
+// Each member writes the row-major result of its stripes at the end (copy_out_own).
 struct TbLayout {
-  int pitch;  // bricks per brick row (AF_BRICK) or the row pitch
-  AF_DEV int at(int z, int x) const {
-#if AF_BRICK
-    return (((z >> 2) * pitch + (x >> 2)) << 4) | ((z & 3) << 2) | (x & 3);
-#else
-    return z * pitch + x;
-#endif
-  }
+  int pitch;  // bricks per brick row
+  AF_DEV int at(int z, int x) const { return (((z >> 2) * pitch + (x >> 2)) << 4) | ((z & 3) << 2) | (x & 3); }
   // at(z, x) == zpart(z) + xpart(x): the bit fields do not overlap, so a stencil's 12 indices
   // are sums of 5 row parts and 5 column parts
-  AF_DEV int zpart(int z) const {
-#if AF_BRICK
-    return (z >> 2) * (pitch << 4) + ((z & 3) << 2);
-#else
-    return z * pitch;
-#endif
-  }
-  AF_DEV int xpart(int x) const {
-#if AF_BRICK
-    return ((x >> 2) << 4) + (x & 3);
-#else
-    return x;
-#endif
-  }
+  AF_DEV int zpart(int z) const { return (z >> 2) * (pitch << 4) + ((z & 3) << 2); }
+  AF_DEV int xpart(int x) const { return ((x >> 2) << 4) + (x & 3); }
 };
-// stencil indices from the separable row / column parts (1) or per point (0): boundary cells
-// (load_nb) and interior cells (load_tb)
-#ifndef AF_NB_SEP
-#define AF_NB_SEP 1
-#endif
-#ifndef AF_TB_SEP
-#define AF_TB_SEP 0
-#endif
 
 // Working field -> row-major result for the stripes member `me` owns (s = me, me + K, ...; stripe
 // widths are multiples of 4, so bricks never straddle two owners).  Item = one 4 x 4 brick: one
@@ -301,7 +152,7 @@ AF_DEV void copy_out_own(double* __restrict__ T, const double* __restrict__ Tb, 
   const int nown = (nstr - me + g.K - 1) / g.K;
   const int qlog = g.wlog - 2;  // bricks per stripe row: 1 << qlog
   const long nq = (long)((nz + 3) >> 2) * nown << qlog;
-  const bool vec = AF_BRICK && (nx & 3) == 0;
+  const bool vec = (nx & 3) == 0;
   for (long q = tid; q < nq; q += kThreads) {
     const int c = (int)(q & ((1 << qlog) - 1));
     const long r = q >> qlog;
@@ -327,18 +178,12 @@ AF_DEV void copy_out_own(double* __restrict__ T, const double* __restrict__ Tb, 
 }
 
 // The band kernel's status array Sb (far -1, known 0, close 1 + close-set slot; per source, in
-// the arena): AF_BRICK stores 4 x 8 bricks of int32, one 128-byte line each (claim items — the
-// 4-neighbours of tile-ordered accepted cells — then touch 0.17 instead of 0.31 lines per item on
-// the C4 front); 0 is row-major.
+// the arena): 4 x 8 bricks of int32, one 128-byte line each (claim items — the 4-neighbours of
+// tile-ordered accepted cells — then touch 0.17 instead of a row-major array's 0.31 lines per
+// item on the C4 front).
 struct SbLayout {
-  int pitch;  // bricks per brick row (AF_BRICK) or the row pitch
-  AF_DEV int at(int z, int x) const {
-#if AF_BRICK
-    return (((z >> 2) * pitch + (x >> 3)) << 5) | ((z & 3) << 3) | (x & 7);
-#else
-    return z * pitch + x;
-#endif
-  }
+  int pitch;  // bricks per brick row
+  AF_DEV int at(int z, int x) const { return (((z >> 2) * pitch + (x >> 3)) << 5) | ((z & 3) << 3) | (x & 7); }
 };
 
 // known: 0 (hand-over) or the acceptance stamp -(2 + step); far -1; close 1 + slot
@@ -353,20 +198,10 @@ AF_DEV void load_tb(NbFieldT& nb, const double* Tb, const TbLayout& L, int nz, i
   nb.iz = z;
   nb.ix = x;
   double t[12];
-  if (AF_TB_SEP) {
-    int zp[5], xp[5];
 #pragma unroll
-    for (int r = 0; r < 5; r++) zp[r] = L.zpart(min(max(z + r - 2, 0), nz - 1));
-#pragma unroll
-    for (int c = 0; c < 5; c++) xp[c] = L.xpart(min(max(x + c - 2, 0), nx - 1));
-#pragma unroll
-    for (int k = 0; k < 12; k++) t[k] = gld(Tb + (zp[dz[k] + 2] + xp[dx[k] + 2]));
-  } else {
-#pragma unroll
-    for (int k = 0; k < 12; k++) {
-      const int zz = min(max(z + dz[k], 0), nz - 1), xx = min(max(x + dx[k], 0), nx - 1);
-      t[k] = gld(Tb + L.at(zz, xx));
-    }
+  for (int k = 0; k < 12; k++) {
+    const int zz = min(max(z + dz[k], 0), nz - 1), xx = min(max(x + dx[k], 0), nx - 1);
+    t[k] = gld(Tb + L.at(zz, xx));
   }
   unsigned m = 0;
 #pragma unroll
@@ -394,7 +229,7 @@ AF_DEV void load_nb(NbFieldT& nb, const double* T, const TbLayout& L, int eprv, 
 #pragma unroll
   for (int r = 0; r < 5; r++) zc[r] = min(max(z + r - 2, 0), g.nz - 1);  // rows z-2 .. z+2 (clamped)
   int idx[12];
-  if (AF_NB_SEP) {
+  {
     // own points: row part + column part; a column across the stripe boundary (at most the two
     // on one side: stripes are >= 8 wide) is edge-buffer column ecol(x + dx) = e0 + dx, with e0
     // from this cell's stripe s and offset r: s * 4 + r on the left edge, s * 4 + r + 4 - W on the right
@@ -413,18 +248,6 @@ AF_DEV void load_nb(NbFieldT& nb, const double* T, const TbLayout& L, int eprv, 
       const int r = dz[k] + 2, c = dx[k] + 2;
       idx[k] = ot[c] ? cb[c] + zc[r] : zp[r] + cb[c];  // (in range: no clamp)
     }
-  } else {
-#pragma unroll
-    for (int c = 0; c < 5; c++) {  // columns x-2 .. x+2: own (working field) or edge buffer (column-major)
-      ot[c] = g.other(x, c - 2);
-      cb[c] = ot[c] ? eprv + g.ecol(x + c - 2) * g.nz : min(max(x + c - 2, 0), g.nx - 1);
-    }
-#pragma unroll
-    for (int k = 0; k < 12; k++) {
-      const int r = dz[k] + 2, c = dx[k] + 2;
-      const int i = ot[c] ? cb[c] + zc[r] : L.at(zc[r], cb[c]);
-      idx[k] = i < 0 ? 0 : i >= total ? total - 1 : i;
-    }
   }
   double t[12];
   // 32-bit byte offsets (scalar base + vector offset form) while field + edge buffers stay below
@@ -434,11 +257,10 @@ AF_DEV void load_nb(NbFieldT& nb, const double* T, const TbLayout& L, int eprv, 
 #pragma unroll
     for (int k = 0; k < 12; k++) {
       const double* a = (const double*)((const char*)T + ((unsigned)idx[k] << 3));
-      // AF_NB_MIX: own-column points (this member's field: plain loads see its own stores) 1: the
-      // cell's own column plain, 2: every own point plain
-      if (AF_NB_MIX >= 1 && dx[k] == 0) t[k] = fabs(gld(a));
-      else if (AF_NB_MIX == 2) t[k] = fabs(ot[dx[k] + 2] ? gld_sc1(a) : gld(a));
-      else t[k] = fabs(gld_sc1(a));
+      // own points (this member's field: plain loads see its own stores) plain, the cell's own
+      // column (never another member's) without the test
+      if (dx[k] == 0) t[k] = fabs(gld(a));
+      else t[k] = fabs(ot[dx[k] + 2] ? gld_sc1(a) : gld(a));
     }
   } else {
 #pragma unroll
@@ -456,9 +278,8 @@ AF_DEV void load_nb(NbFieldT& nb, const double* T, const TbLayout& L, int eprv, 
 // fouds18_A() reads a 5x5 neighbourhood with "known" = status 0 after this step's acceptance.  The
 // (rare) fallback cells are processed in rounds: all threads stage each cell's neighbourhood into
 // LDS — T at the end of the previous step (NaN -> 0 as GField) and known-ness (own cell: status 0;
-// another member's: known in the previous edge buffer, or close with T <= thr) — then one lane per
-// cell runs fouds18_A() on the staged window (few registers: the accessor is two LDS reads).
-constexpr int kFbRound = AF_FB_ROUND;  // cells per staging round (25 doubles each in the claim-hash space)
+// another member's: known in the previous edge buffer, or close with T <= thr) — then four lanes
+// per cell run fouds18_A() on the staged window (few registers: the accessor is two LDS reads).
 static_assert(kFbRound * 25 * sizeof(double) <= kHashArr * sizeof(int), "staging windows fit H");
 struct Win5 {
   const double* t;  // 25 values, row-major (dz + 2) * 5 + (dx + 2)
@@ -467,23 +288,6 @@ struct Win5 {
   AF_DEV int st(long z, long x) const { return (known >> ((z - iz + 2) * 5 + (x - ix + 2))) & 1u ? (int)kKnown : -1; }
   AF_DEV double tt(long z, long x) const { return t[(z - iz + 2) * 5 + (x - ix + 2)]; }
 };
-
-// fouds18_A() on a staged window, out of line: the fallback runs for a few per cent of the cells,
-// and one shared copy keeps its ~30 KB of code out of the step loop's instruction-cache working set
-#ifndef AF_F18_OUTLINE
-#define AF_F18_OUTLINE 0
-#endif
-#if AF_F18_OUTLINE
-#define AF_F18_ATTR __attribute__((noinline))
-#else
-#define AF_F18_ATTR __forceinline__
-#endif
-template <bool PRE_ONLY>
-__device__ AF_F18_ATTR double fouds18_w5(const Win5& F, const DevModel& M, const CellMat& cm, int z,
-                                                      int x, double dnx, double dnz, int nx, int nz,
-                                                      const double* pre) {
-  return fouds18<PRE_ONLY>(F, M, cm, z, x, dnx, dnz, nx, nz, pre);
-}
 
 // Host streaming.  Tiles are W columns (one stripe) x TR = 2^tr_log rows; member me's own tiles
 // are numbered o = tz * nown + js (stripe s = me + js K).  A tile whose cells are all known is
@@ -552,21 +356,20 @@ AF_DEV void st_sys8(unsigned long long* p, double a) {
 }
 
 // list b's tiles' cells -> their ring slots (tile i0 + k of the member for entry k; every thread;
-// loads of AF_HS_U items, then their stores).  An item is one cell (AF_HS_VEC 0) or two adjacent
-// cells of a row (1); consecutive lanes take consecutive items of a tile, so one wave instruction
+// loads of kHsU items, then their stores).  An item is two adjacent cells of a row (one 16-byte
+// system-scope store); consecutive lanes take consecutive items of a tile, so one wave instruction
 // writes a contiguous piece of the slot
 AF_DEV void stage_tiles(const Lds* sh, int n, int b, int i0, const TileStream& ts, const double* Tb,
                         const TbLayout& TL, int tid) {
-  constexpr int kV = AF_HS_VEC ? 2 : 1;
   const int clog = ts.wlog + ts.trlog;
-  const int ilog = clog - (kV - 1), rlog = ts.wlog - (kV - 1);  // items per tile / row (log2)
+  const int ilog = clog - 1, rlog = ts.wlog - 1;  // items per tile / row (log2)
   const long total = (long)n << ilog;
-  for (long q0 = tid; q0 < total; q0 += (long)AF_HS_U * kThreads) {
-    double v0[AF_HS_U], v1[AF_HS_U];
-    long d[AF_HS_U];
-    int w[AF_HS_U];  // cells of the item inside the grid (0, 1, 2)
+  for (long q0 = tid; q0 < total; q0 += (long)kHsU * kThreads) {
+    double v0[kHsU], v1[kHsU];
+    long d[kHsU];
+    int w[kHsU];  // cells of the item inside the grid (0, 1, 2)
 #pragma unroll
-    for (int u = 0; u < AF_HS_U; u++) {
+    for (int u = 0; u < kHsU; u++) {
       const long q = q0 + (long)u * kThreads;
       d[u] = 0;
       w[u] = 0;
@@ -576,10 +379,10 @@ AF_DEV void stage_tiles(const Lds* sh, int n, int b, int i0, const TileStream& t
         int z0, x0;
         ts.origin(sh->Td[b][k], z0, x0);
         const int r = (int)(q & ((1L << ilog) - 1));
-        const int zr = r >> rlog, xr = kV * (r & ((1 << rlog) - 1));
+        const int zr = r >> rlog, xr = 2 * (r & ((1 << rlog) - 1));
         const int z = z0 + zr, x = x0 + xr;
         if (z < ts.nz && x < ts.nx) {
-          w[u] = (kV == 2 && x + 1 < ts.nx) ? 2 : 1;
+          w[u] = x + 1 < ts.nx ? 2 : 1;
           v0[u] = gld(Tb + TL.at(z, x));
           if (w[u] == 2) v1[u] = gld(Tb + TL.at(z, x + 1));
           d[u] = ((long)((i0 + k) % ts.rslots) << clog) + (zr << ts.wlog) + xr;
@@ -587,7 +390,7 @@ AF_DEV void stage_tiles(const Lds* sh, int n, int b, int i0, const TileStream& t
       }
     }
 #pragma unroll
-    for (int u = 0; u < AF_HS_U; u++) {
+    for (int u = 0; u < kHsU; u++) {
       if (w[u] == 2) {
         st_sys16(ts.ring + d[u], v0[u], v1[u]);
       } else if (w[u] == 1) {
@@ -617,16 +420,13 @@ AF_DEV void publish_tiles(Lds* sh, const TileStream& ts, int b, int lane) {
 // word per lane) until every member's words carry this step's tag, then the wave reduces them:
 // global Tmin, live close cells (sum), error (or), and the neighbour members' rim-list lengths.
 // false on timeout (a member is not resident)
-// XCD-local cross-member data (AF_XCD_LOCAL): once every member of a source has reported the same
+// XCD-local cross-member data: once every member of a source has reported the same
 // XCD (HW_REG_XCC_ID, carried in its exchange word 2), the members' edge buffers, rim lists
 // and exchange words are stored plainly instead of write-through (sc1): the stores complete in the
 // XCD's L2, which the readers' sc1 (L1-bypassing) loads are served from, instead of travelling to
 // memory and dropping the line from L2.  Placement is read, not assumed: members on different XCDs
 // keep the sc1 stores (MI355X_MICROARCH.md "inter-workgroup visibility").  BandParams::xcd_local 0
 // (option "xcd_local") keeps them on one XCD as well: the write-through exchange under test.
-#ifndef AF_XCD_LOCAL
-#define AF_XCD_LOCAL 1
-#endif
 AF_DEV int xcc_id() {
   int v;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(v));
@@ -634,7 +434,7 @@ AF_DEV int xcc_id() {
 }
 template <class T>
 AF_DEV void xst(T* p, T v, bool loc) {
-  if (AF_XCD_LOCAL && loc) gst(p, v);
+  if (loc) gst(p, v);
   else gst_sc1(p, v);
 }
 
@@ -650,7 +450,7 @@ AF_DEV bool x1_poll(KX* X, int K, int par, unsigned tag, Lds* sh, int mprev, int
       ok = (unsigned)(v >> 32) == tag;
     }
     if (__all(ok)) break;
-    if (AF_X1_SLEEP) __builtin_amdgcn_s_sleep(AF_X1_SLEEP);
+    __builtin_amdgcn_s_sleep(1);
     if (++spins > (1L << 25)) return false;
   }
   const unsigned w = (unsigned)v;
@@ -683,20 +483,8 @@ AF_DEV bool x1_poll(KX* X, int K, int par, unsigned tag, Lds* sh, int mprev, int
 }
 
 template <int MODE, bool LDSMAT, bool PROF>
-// 3 waves per SIMD (<= 168 VGPRs) in both layouts: 12 waves per CU = one 768-thread or two
-// 384-thread members
-#ifndef AF_WPE
-#define AF_WPE 1
-#endif
-#ifndef AF_WPE_N
-#define AF_WPE_N 3  // waves per SIMD the registers are sized for
-#endif
-#if AF_WPE
-#define AF_WPE_ATTR __attribute__((amdgpu_waves_per_eu(AF_WPE_N)))
-#else
-#define AF_WPE_ATTR
-#endif
-__global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandParams P) {
+// registers sized for 3 waves per SIMD (<= 168 VGPRs): 12 waves per CU = one 768-thread member
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) void fmm_band_k_kernel(BandParams P) {
   __shared__ Lds sh_;
   Lds* sh = &sh_;
   const int K = P.K;
@@ -787,9 +575,7 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
     // two lists could wait for the host forever (tile_stream.h kRingSlots)
     if (hstream && P.rslots < 2 * kTdCap) sh->err = 11;
   }
-#if AF_SORT_ACC
   for (int k = tid; k < kSortB; k += kThreads) sh->Sb[k] = 0;  // (re-zeroed after each sort)
-#endif
   __syncthreads();
   // ---------------- hand-over: own cells only ----------------
   if (MODE == 0) {
@@ -942,9 +728,6 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
         }
       }
     }
-#if AF_PROF_SEG == 1
-    if (prof) sub[2] += wall_clock64() - tk;
-#endif
     tmin = wave_min_full(tmin);
     if (lane == 0) sh->red[wv] = tmin;
     if (tid == 0) {
@@ -960,12 +743,7 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
     const long long tdr = prof ? wall_clock64() : 0;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-#if !AF_PROF_FBWAIT && !AF_PROF_SPILL && !AF_PROF_CLAIM && !AF_PROF_SEG
     AF_SUBT(3, tdr)
-#endif
-#if AF_PROF_SEG == 1
-    if (prof) sub[3] += wall_clock64() - tk;
-#endif
     tmin = sh->red[0];
     for (int w = 1; w < kWaves; w++) tmin = fmin(tmin, sh->red[w]);
     const double delta = launder_u(R.delta), t0 = launder_u(R.t0);
@@ -1000,14 +778,10 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
     if (tid == 0 && steps >= P.max_steps) sh->err = 8;  // a band that never finishes (cannot happen
                                                        // with valid inputs): stop instead of hanging
     __syncthreads();
-#if !AF_PROF_EVW
     AF_SUBT(0, tx1)
-#endif
     AF_TICK(0)
     if (sh->live_g <= 0 || sh->err_g || sh->err) break;
-#if !AF_PROF_CLAIM && !AF_PROF_SEG && !AF_PROF_EVW
     if (prof) sub[2] += sh->xl ? 100 : 0;  // steps whose exchange was XCD-local (x 100; of steps[3])
-#endif
     // ---- P0: last step's accepted edge cells into this step's edge buffer.  Only now: every member
     // has passed this step's X1, i.e. finished the previous step, which read this buffer.  The
     // list is the last step's parity (this step's acceptance fills the other one: no barrier) ----
@@ -1022,16 +796,10 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
         xst(Epar + g.eidx(pkz(c), pkx(c)), -DVp.get(d), (bool)sh->xl);
       }
     }
-#if AF_PROF_SEG == 2
-    if (prof) sub[2] += wall_clock64() - tk;
-#endif
     tmin = sh->tmin_g;
     double dl = delta;
     if (t0 > 0 && tmin < t0) dl = delta * (tmin / t0);
-#ifndef AF_FAR
-#define AF_FAR 1
-#endif
-    if (AF_FAR) {  // wider band far from the source (options cdelta_far / r_far: 0.6 beyond 256 nodes)
+    {  // wider band far from the source (options cdelta_far / r_far: 1.4 x the width beyond 768 nodes)
       const double tfar = launder_u(R.tfar);
       if (tfar > 0 && tmin > tfar) dl = delta + (launder_u(R.delta_far) - delta) * fmin(1.0, (tmin - tfar) / tfar);
     }
@@ -1121,9 +889,6 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
     };
     if (hi <= kLcap) accept(std::true_type{});
     else accept(std::false_type{});
-#if AF_PROF_SEG == 2
-    if (prof) sub[3] += wall_clock64() - tk;
-#endif
     // ---- P3a: the neighbour members' accepted rim cells -> claim items (their cross neighbour) ----
     const long long trr = prof ? wall_clock64() : 0;
     if (K > 1) {
@@ -1152,15 +917,15 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
       }
     }
     __syncthreads();
-#if !AF_PROF_EVW
     AF_SUBT(1, trr)
-#endif
     AF_TICK(1)
     const int nA = min(sh->nA, capL), nRx = min(sh->nRx, capC);
     int* alist = sh->Al;
+    // (tso, tcw and tfw below: clock reads of retired diagnostics, nothing consumes them; they are
+    // instructions of the PROF instantiations, so dropping them is left to a change that may alter
+    // the profile build's code)
     const long long tso = prof ? wall_clock64() : 0;
-#if AF_SORT_ACC
-    if (nA > AF_SORT_ACC && nA <= kAcap && K <= AF_SORT_KMAX) {  // (uniform) counting sort of the accepted list by tile
+    if (nA > kSortAcc && nA <= kAcap && K <= kSortKmax) {  // (uniform) counting sort of the accepted list by tile
       for (int a = tid; a < nA; a += kThreads) atomicAdd(&sh->Sb[tile_bucket(sh->Al[a])], 1);
       __syncthreads();
       static_assert(kSortB % 64 == 0 && kSortB / 64 <= kWaves, "one bucket per thread of the first waves");
@@ -1183,10 +948,6 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
       for (int k = tid; k < kSortB; k += kThreads) sh->Sb[k] = 0;
       alist = sh->As;
     }
-#endif
-#if AF_PROF_CLAIM
-    AF_SUBT(2, tso)
-#endif
     // ---- P3b: claim ----
     const int nItems = 4 * nA + nRx;
     const bool lds_items = nA <= kAcap && nRx <= kRcap;
@@ -1235,9 +996,9 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
       // another member exactly when it lies across a stripe boundary
       const int W1 = (1 << g.wlog) - 1;
       const bool one = K == 1;
-      // kCU items per lane and pass; one (AF_CLAIM_ADAPT) when one pass of one item per thread
-      // holds them all: a second item's instructions would issue for nothing (16 sources: 117.9 ->
-      // 115.6 ms; a one-item last pass after full ones measured slower, profiles/r6x/kab_claim_adapt*)
+      // kCU items per lane and pass; one when one pass of one item per thread holds them all: a
+      // second item's instructions would issue for nothing (16 sources: 117.9 -> 115.6 ms; a
+      // one-item last pass after full ones measured slower, profiles/r6x/kab_claim_adapt*)
       auto claim_pass = [&](auto ucount, int qa, int qb) {
         constexpr int kU = decltype(ucount)::value;
         for (int q0 = qa; q0 < qb; q0 += kThreads * kU) {
@@ -1282,20 +1043,11 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
 #pragma unroll
           for (int u = 0; u < kU; u++) {
             const int c = max(r[u], 0), xi = pkx(c) & 7, zi = pkz(c) & 3, i0 = si[u];
-  #if AF_BRICK
             s[u] = r[u] >= 0 ? gld(Sb + i0) : (int)kKnown;
             pn[u][0] = (pm[u] & 1u) ? gld(Sb + i0 + (xi != 7 ? 1 : 25)) : 0;
             pn[u][1] = (pm[u] & 2u) ? gld(Sb + i0 - (xi != 0 ? 1 : 25)) : 0;
             pn[u][2] = (pm[u] & 4u) ? gld(Sb + i0 + (zi != 3 ? 8 : zstep)) : 0;
             pn[u][3] = (pm[u] & 8u) ? gld(Sb + i0 - (zi != 0 ? 8 : zstep)) : 0;
-  #else
-            s[u] = r[u] >= 0 ? gld(Sb + i0) : (int)kKnown;
-            const int z = pkz(c), x = pkx(c);
-            pn[u][0] = (pm[u] & 1u) ? gld(Sb + SL.at(z, x + 1)) : 0;
-            pn[u][1] = (pm[u] & 2u) ? gld(Sb + SL.at(z, x - 1)) : 0;
-            pn[u][2] = (pm[u] & 4u) ? gld(Sb + SL.at(z + 1, x)) : 0;
-            pn[u][3] = (pm[u] & 8u) ? gld(Sb + SL.at(z - 1, x)) : 0;
-  #endif
           }
 #pragma unroll
           for (int u = 0; u < kU; u++) {
@@ -1304,50 +1056,32 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
           }
         }
       };
-      if (AF_CLAIM_ADAPT && nItems <= kThreads) claim_pass(std::integral_constant<int, 1>{}, 0, nItems);
+      if (nItems <= kThreads) claim_pass(std::integral_constant<int, 1>{}, 0, nItems);
       else claim_pass(std::integral_constant<int, kCU>{}, 0, nItems);
     }
     // this step's edge-buffer stores (accept scan, P0) precede this step's commits to the same
     // addresses (a wave that issued no load since has not waited for them yet)
     const long long tcw = prof ? wall_clock64() : 0;
-#ifndef AF_DRAIN_LATE
-#define AF_DRAIN_LATE 0
-#endif
-    // (AF_DRAIN_LATE: the same wait placed before the commit's barrier instead, where the stores
-    // have long completed)
-    if (K > 1 && !AF_DRAIN_LATE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (K > 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-#if AF_PROF_CLAIM
-    AF_SUBT(3, tcw)
-#endif
     const int nEi = min((int)(unsigned)sh->nE2, capC);
     const int nEb = min((int)(unsigned)(sh->nE2 >> 32), capC - nEi);
-    if (!AF_BL_INPLACE && nEb > 0) {  // boundary cells after the interior ones
-      for (int j2 = tid; j2 < nEb; j2 += kThreads) {
-        EL.put(nEi + j2, BL.get(j2));
-        EP.put(nEi + j2, BP.get(j2));
-      }
-      __syncthreads();
-    }
     AF_TICK(2)
-#if AF_PROF_EVW
-    const long long tev0 = PROF ? wall_clock64() : 0;
-#endif
     const int nE = nEi + nEb;
-    // the claimed cells as one list: interior (EL / EP), then boundary (BL / BP), read in place
-    // (AF_BL_INPLACE) or from EL / EP after the copy above; VL and the fallback list index it
+    // the claimed cells as one list: interior (EL / EP), then boundary (BL / BP), read in place;
+    // VL and the fallback list index it
     auto cellE = [&](int e, auto lds_only) {
       constexpr bool LO = decltype(lds_only)::value;
-      if (AF_BL_INPLACE && e >= nEi) return LO ? BL.lds(e - nEi) : BL.get(e - nEi);
+      if (e >= nEi) return LO ? BL.lds(e - nEi) : BL.get(e - nEi);
       return LO ? EL.lds(e) : EL.get(e);
     };
     auto slotE = [&](int e, auto lds_only) {
       constexpr bool LO = decltype(lds_only)::value;
-      if (AF_BL_INPLACE && e >= nEi) return LO ? BP.lds(e - nEi) : BP.get(e - nEi);
+      if (e >= nEi) return LO ? BP.lds(e - nEi) : BP.get(e - nEi);
       return LO ? EP.lds(e) : EP.get(e);
     };
     // ---- P4: evaluate ----
-    const bool lds_e = nE <= kEcap && (!AF_BL_INPLACE || nEb <= kBcap);  // (uniform) every list in LDS
+    const bool lds_e = nE <= kEcap && nEb <= kBcap;  // (uniform) every list in LDS
     const double dnx_e = launder_u(R.dnx);
     auto eval_done = [&](int e, double v) {
       if (lds_e) VL.put_lds(e, v);
@@ -1363,58 +1097,23 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
         if (v == -1.0 && fb < kRcap) sh->Rx[fb] = e;
       }
     };
-    // stencil loads first, then the material id: one memory round trip per cell.  Pass order
-    // (AF_EVAL_BFIRST): the boundary cells (the list's tail; their edge-buffer lines come from
-    // further away) go to the first pass's lanes, so their latency overlaps the interior passes
-    // instead of trailing the phase.  Every wave whose cells are all interior loads T only.
-    for (int j = tid; j < nE; j += kThreads) {
-      const int e = AF_EVAL_BFIRST ? (j < nEb ? nEi + j : j - nEb) : j;
-      const bool interior = AF_EVAL_BFIRST ? j - lane >= nEb : e - lane + 64 <= nEi;  // (wave-uniform)
+    // stencil loads first, then the material id: one memory round trip per cell.  The boundary
+    // cells (the list's tail) go last (first measured slower).  Every wave whose
+    // cells are all interior loads T only.
+    for (int e = tid; e < nE; e += kThreads) {
+      const bool interior = e - lane + 64 <= nEi;  // (wave-uniform)
       const int r = lds_e ? cellE(e, std::true_type{}) : cellE(e, std::false_type{});
       const int z = pkz(r), x = pkx(r);
       NbFieldT nb;
       if (interior) load_tb(nb, Tb, TL, nz, nx, z, x);
       else load_nb(nb, Tb, TL, eprv, tbc + 2 * ecells, g, z, x);
       const CellMat cm = band_mat<LDSMAT, MODE == 0>(M, sh->mat, sh->stab, R.mv, z, x);
-#if AF_DIAG_DBL  // diagnostic: a second, opaque update() per cell (its marginal cost), same results
-      NbFieldT nb2 = nb;
-      double d0 = nb.t0;
-      asm volatile("" : "+v"(d0));
-      nb2.t0 = d0;
-      const double v2 = update(nb2, M, cm, z, x, dnx_e, nz, nx);
-      eval_done(e, update(nb, M, cm, z, x, dnx_e, nz, nx) + 0.0 * v2);
-#else
       eval_done(e, update(nb, M, cm, z, x, dnx_e, nz, nx));
-#endif
     }
     AF_TICK(3)
-#if AF_PROF_EVW
-    if (PROF && me == 0 && lane == 0) {
-      sh->evt[wv] = wall_clock64();
-      sh->evb[wv] = wv * 64 >= nE ? 0 : (wv * 64 + 63 >= nEi ? 2 : 1);
-    }
-#endif
     // ---- P4b: fouds18_A() over the compacted fallback list, in staged rounds ----
     const long long tfw = prof ? wall_clock64() : 0;
     __syncthreads();
-#if AF_PROF_EVW
-    if (prof) {
-      long long ti = 0, tb = 0;
-      for (int w = 0; w < kWaves; w++) {
-        if (sh->evb[w] == 1) ti = max(ti, sh->evt[w] - tev0);
-        if (sh->evb[w] == 2) tb = max(tb, sh->evt[w] - tev0);
-      }
-      if (ti > 0 && tb > 0) {  // steps with both kinds of wave
-        sub[2] += ti;
-        sub[3] += tb;
-        sub[1] += 100;
-      }
-      sub[0] += sh->xl ? 100 : 0;    // (kbench: fraction of steps with XCD-local exchange)
-    }
-#endif
-#if AF_PROF_FBWAIT  // diagnostic: sub[3] = the wait for the other waves' evaluation
-    AF_SUBT(3, tfw)
-#endif
     {
       const int nFb = sh->nFb;
       const double thr_f = thr;
@@ -1450,42 +1149,27 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
           if (kn) atomicOr(&wmask[i / 25], 1u << o);
         }
         __syncthreads();
-        if (AF_F18_SPLIT) {
-          // four lanes per cell, one candidate of each stencil family per lane (fouds18_part)
-          static_assert(4 * kFbRound <= kThreads, "four lanes per fallback cell");
-          if (tid < 4 * nr) {
-            const int ci = tid >> 2, part = tid & 3;
-            const int q = r0 + ci;
-            const int e = q < nlist ? sh->Rx[q] : q - nlist;
-            if (q < nlist || VL.get(e) == -1.0) {  // (the same for the cell's four lanes)
-              const int c = cellE(e, std::false_type{});
-              const int z = pkz(c), x = pkx(c);
-              const Win5 F{win + 25 * ci, wmask[ci], z, x};
-              const CellMat cm = band_mat<LDSMAT, MODE == 0>(M, sh->mat, sh->stab, R.mv, z, x);
-              const double dnx_f = launder_u(R.dnx), dnz_f = launder_u(R.dnz);
-              F18Part fp = fouds18_part<LDSMAT>(F, M, cm, z, x, dnx_f, dnz_f, nx, nz, mat_slo(M, R.mv, z, x), part);
-#pragma unroll
-              for (int o = 1; o <= 2; o <<= 1) {
-                F18Part ot;
-#pragma unroll
-                for (int k = 0; k < 4; k++) ot.m[k] = __shfl_xor(fp.m[k], o);
-                fp = f18_min(fp, ot);
-              }
-              if (part == 0) VL.put(e, fouds18_combine(fp, F.tt(z, x)));
-            }
-          }
-        } else if (tid < nr) {
-          const int q = r0 + tid;
+        // four lanes per cell, one candidate of each stencil family per lane (fouds18_part)
+        static_assert(4 * kFbRound <= kThreads, "four lanes per fallback cell");
+        if (tid < 4 * nr) {
+          const int ci = tid >> 2, part = tid & 3;
+          const int q = r0 + ci;
           const int e = q < nlist ? sh->Rx[q] : q - nlist;
-          if (q < nlist || VL.get(e) == -1.0) {
+          if (q < nlist || VL.get(e) == -1.0) {  // (the same for the cell's four lanes)
             const int c = cellE(e, std::false_type{});
             const int z = pkz(c), x = pkx(c);
-            const Win5 F{win + 25 * tid, wmask[tid], z, x};
+            const Win5 F{win + 25 * ci, wmask[ci], z, x};
             const CellMat cm = band_mat<LDSMAT, MODE == 0>(M, sh->mat, sh->stab, R.mv, z, x);
             const double dnx_f = launder_u(R.dnx), dnz_f = launder_u(R.dnz);
-            double v;
-            v = fouds18_w5<LDSMAT>(F, M, cm, z, x, dnx_f, dnz_f, nx, nz, mat_slo(M, R.mv, z, x));
-            VL.put(e, v);
+            F18Part fp = fouds18_part<LDSMAT>(F, M, cm, z, x, dnx_f, dnz_f, nx, nz, mat_slo(M, R.mv, z, x), part);
+#pragma unroll
+            for (int o = 1; o <= 2; o <<= 1) {
+              F18Part ot;
+#pragma unroll
+              for (int k = 0; k < 4; k++) ot.m[k] = __shfl_xor(fp.m[k], o);
+              fp = f18_min(fp, ot);
+            }
+            if (part == 0) VL.put(e, fouds18_combine(fp, F.tt(z, x)));
           }
         }
         __syncthreads();
@@ -1493,10 +1177,6 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
     }
     // (no barrier here: the one before the fallback rounds, or the last round's, already separates
     // every evaluation and fallback write from the commit)
-    if (K > 1 && AF_DRAIN_LATE) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
     AF_TICK(4)
     // ---- P5: commit own cells; edge cells also into this step's edge buffer (slot marked DIRTY:
     // the next step's accept scan copies them forward) ----
@@ -1545,7 +1225,7 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
         }
       }
     };
-    if (nE <= kEcap && (!AF_BL_INPLACE || nEb <= kBcap) && hi + nE <= kLcap) commit(std::true_type{});
+    if (nE <= kEcap && nEb <= kBcap && hi + nE <= kLcap) commit(std::true_type{});
     else commit(std::false_type{});
     __syncthreads();
     // No barrier at the step's end: the next step's first reads of what this end writes are behind
@@ -1563,10 +1243,6 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
       ls[1] += nA;
       ls[2] += nE;
       lmax = max(lmax, (long long)hi);
-#if AF_PROF_SPILL  // diagnostic: sub[3] counts the steps whose lists outgrew their LDS heads
-      sub[3] += (sh->nA > kAcap ? 1 : 0) + (nE > kEcap ? 1000 : 0) + (hi > kLcap ? 1000000 : 0) +
-                0LL;
-#endif
     }
     steps++;
     AF_TICK(5)
@@ -1632,19 +1308,13 @@ __global__ __launch_bounds__(kThreads) AF_WPE_ATTR void fmm_band_k_kernel(BandPa
 }  // namespace kb
 }  // namespace af
 
-// band-kernel workgroups one CU holds at once (the host sizes K so that every member is resident)
-extern "C" int af_band_wgs_per_cu() { return AF_WG_PER_CU; }
+// the brick layouts' pitches (bricks per brick row) and sizes (TbLayout: 4 x 4, SbLayout: 4 x 8)
+extern "C" int af_band_tb_pitch(int nx) { return (nx + 3) / 4; }
+extern "C" int af_band_sb_pitch(int nx) { return (nx + 7) / 8; }
+extern "C" long af_band_sb_cells(int nz, int nx) { return 32L * ((nz + 3) / 4) * ((nx + 7) / 8); }
+extern "C" long af_band_tb_cells(int nz, int nx) { return 16L * ((nz + 3) / 4) * ((nx + 3) / 4); }
 
-extern "C" int af_band_tb_pitch(int nx) { return AF_BRICK ? (nx + 3) / 4 : nx; }
-extern "C" int af_band_sb_pitch(int nx) { return AF_BRICK ? (nx + 7) / 8 : nx; }
-extern "C" long af_band_sb_cells(int nz, int nx) {
-  return AF_BRICK ? 32L * ((nz + 3) / 4) * ((nx + 7) / 8) : (long)nz * nx;
-}
-extern "C" long af_band_tb_cells(int nz, int nx) {
-  return AF_BRICK ? 16L * ((nz + 3) / 4) * ((nx + 3) / 4) : (long)nz * nx;
-}
-
-// nsrc (padded to a multiple of 8) x K workgroups, AF_WG_PER_CU per CU, all resident
+// nsrc (padded to a multiple of 8) x K workgroups, one per CU, all resident
 extern "C" hipError_t af_launch_band_k(const af::BandParams* P, hipStream_t stream) {
   const bool lds = P->M.mid && P->M.mslo && P->M.nmat <= af::kb::kMatLds && P->M.nstab <= af::kb::kStabLds &&
                    361 * P->M.ncol <= af::kb::kPtabLds;
@@ -1666,7 +1336,7 @@ extern "C" hipError_t af_launch_band_k(const af::BandParams* P, hipStream_t stre
   if (P->coop) return hipLaunchCooperativeKernel(fn, g, b, args, 0, stream);
   // Plain launch: the members of a source wait for each other every step, so every workgroup must
   // be resident at once — checked here against the occupancy of this kernel (the grid is sized to
-  // it: K from af_band_wgs_per_cu and the CU count).  A cooperative launch checks the same and
+  // it: K from one member per CU and the CU count).  A cooperative launch checks the same and
   // gang-schedules on a dedicated queue; the plain launch avoids that queue, whose teardown at
   // process exit crashed every rocprofv3-traced run (the profiler's queue interception is gone by
   // then).  A member that still never sees its peers stops at the X1 spin limit (error 7).

@@ -34,14 +34,7 @@ namespace xl {
 
 constexpr int kThreads = 256;  // 4 waves clear and hand over; wave 0 walks
 #ifndef AF_XL_DIAG
-#define AF_XL_DIAG 0  // diagnostic build: cycle counters of the walk (walk(), BandSrc::ph / sub)
-#endif
-// a stale speculative entry's stencil stage re-run across the wavefront (1) or on its lane (0)
-#ifndef AF_XL_PARSEL
-#define AF_XL_PARSEL 1
-#endif
-#ifndef AF_XL_TWO_ROLE
-#define AF_XL_TWO_ROLE 1  // heap wavefront + relax wavefront (1), or one wavefront doing both (0)
+#define AF_XL_DIAG 0  // diagnostic build: cycle counters of the two roles (BandSrc::ph)
 #endif
 constexpr int kCap = 163840;   // status nodes (2 bits each): stage grids up to 404 x 404
 constexpr int kHeap = 4096;    // heap slots (1-based)
@@ -226,12 +219,8 @@ struct Heap {
     for (int k = 1; k <= ntr; k++)
       if ((int)(L->ent[k] & kNodeM) == c) L->key[k] = key;
   }
-  // pop the root (its status -> known, its heap-index slot freed unless the node has another
-  // entry), then downtree
-  AF_DEV void pop() {
-    pop_known();
-    pop_rest();
-  }
+  // pop the root in two parts: its status -> known; then its heap-index slot freed (unless the
+  // node has another entry) and downtree
   AF_DEV void pop_known() { sset(L, (int)(L->ent[1] & kNodeM), kSKnown); }
   AF_DEV void pop_rest() {
     const unsigned e0 = L->ent[1];
@@ -370,11 +359,10 @@ AF_DEV void stencil_from_lds(const Lds* L, const Spec& sp, NbFieldT& nb, int lan
 // the job on lane 0, and on every other lane a guess (a neighbour of one of the heap's first 16
 // entries that is not known), each loading its stencil and material from memory.
 AF_DEV double relax_value(Lds* L, const DevModel& M, const XG& g, Spec& sp, int r, int rz, int rx, int ntr,
-                          int lane, long long& npass, int& path) {
+                          int lane, long long& npass) {
   const unsigned long long hm = __ballot(sp.c == r);
   if (hm) {
     const int e = __ffsll((long long)hm) - 1;
-    int pth = 0;
     if (__builtin_amdgcn_readlane((int)sp.dirty, e)) {
       // the patched stencil's stage again, spread over the wavefront (lane k < 12: slot k of the
       // entry's stencil; lanes 0..7 a square stencil each), on the entry's lane where update()
@@ -384,26 +372,22 @@ AF_DEV double relax_value(Lds* L, const DevModel& M, const XG& g, Spec& sp, int 
       const double tk = lane < 12 ? L->stn[lane][e] : 0.0;
       const bool vk = lane < 12 && ((vm_e >> lane) & 1u);
       UpdSel s2;
-      const bool par = AF_XL_PARSEL && update_select_lanes(tk, vk, z_e, x_e, g.nz, g.nx, lane, s2);
+      const bool par = update_select_lanes(tk, vk, z_e, x_e, g.nz, g.nx, lane, s2);
       if (lane == e) {
         if (!par) {
           NbFieldT nb;
           stencil_from_lds(L, sp, nb, lane);
           s2 = update_nb_select(nb, sp.z, sp.x, g.nz, g.nx);
         }
-        pth = 1;
         if (!s2.same(sp.sel)) {
           sp.v = update_nb_finish_ool(M, sp.cm, sp.z, sp.x, g.dnx, s2);
           sp.sel = s2;
-          pth = 2;
         }
         sp.dirty = false;
       }
     }
-    path = __builtin_amdgcn_readlane(pth, e);
     return rlane(sp.v, e);
   }
-  path = 3;
   npass++;
   int cz = rz, cx = rx;
   bool cand = true;
@@ -435,114 +419,27 @@ AF_DEV double relax_value(Lds* L, const DevModel& M, const XG& g, Spec& sp, int 
   return rlane(sp.v, 0);
 }
 
-// The heap walk (:2292-2346, :2460-2504, :2775-2817) on wave 0.  stage: stop when a popped node's
-// neighbour falls off the stage grid at max_dist + 1 from the source; main grid: stop when the
-// root reaches tstop or comes within 3 nodes of a window edge that is not a grid edge.  Returns
-// the pops.
-AF_DEV long long walk(Lds* L, Heap& h, const DevModel& M, const XG& g, bool stage, int isx_s, int isz_s,
-                      int max_dist, double tstop, Spec& sp, int lane, long long* prof, long long* dgo) {
-  long long pops = 0, nrel = 0, npass = 0;
-  // diagnostic build (AF_XL_DIAG): shader-clock cycles of pop, relaxation value by path (clean
-  // entry / stencil stage unchanged / finish / evaluation pass), commit, and the path counts
-  long long dg[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  bool finished = false;
-  while (true) {
-    int go = 0, c = 0, ntr = 0;
-    if (lane == 0) {
-      if (L->nused > (kHT * 3) / 4) go = -1;  // rehash first
-      else go = h.ntr > 0 && !finished && !h.err && !(tstop > 0 && L->key[1] >= tstop);
-      c = (int)(L->ent[1] & kNodeM);
-      ntr = h.ntr;
-    }
-    go = __shfl(go, 0);
-    if (go < 0) {
-      rehash(L, h, lane);
-      continue;
-    }
-    if (!go) break;
-    c = __shfl(c, 0);
-    ntr = __shfl(ntr, 0);
-    const int iz = g.gz(c), ix = g.gx(c);
-    if (!stage && ((g.wz0 > 0 && iz - g.wz0 < 3) || (g.wz0 + g.wh < g.nz && g.wz0 + g.wh - 1 - iz < 3) ||
-                   (g.wx0 > 0 && ix - g.wx0 < 3) || (g.wx0 + g.ww < g.nx && g.wx0 + g.ww - 1 - ix < 3))) {
-      // the window edge before tstop (the root key is still below it): the HBM walk redoes the
-      // source (error 9), so the hand-over is the reference's prefix to tstop
-      if (lane == 0) h.err = 9;
-      break;
-    }  // the window holds no more of the prefix (the band kernel goes on from the heap)
-    // lanes 0..3: neighbour x-1, x+1, z-1, z+1; statuses read before downtree (fmm_exact.hip)
-    const int kz = lane == 2 ? iz - 1 : lane == 3 ? iz + 1 : iz;
-    const int kx = lane == 0 ? ix - 1 : lane == 1 ? ix + 1 : ix;
-    const bool inb = lane < 4 && (lane < 2 ? (0 <= kx && kx <= g.nx - 1) : (0 <= kz && kz <= g.nz - 1));
-    const unsigned st = inb ? sget(L, g.loc(kz, kx)) : kSKnown;
-    const bool edge = lane < 4 && !inb && stage && (lane < 2 ? abs(isx_s - kx) : abs(isz_s - kz)) == max_dist + 1;
-    const unsigned long long jm = __ballot(inb && st != kSKnown);
-    if (__ballot(edge) != 0ull) finished = true;
-    const unsigned long long fm = __ballot(inb && st == kSFar);
-    const long long tp0 = AF_XL_DIAG ? clock64() : 0;
-    if (lane == 0) h.pop();
-    if (AF_XL_DIAG) dg[0] += clock64() - tp0;
-    pops++;
-    for (int k = 0; k < 4; k++) {
-      if (!((jm >> k) & 1ull)) continue;
-      const int rz = k == 2 ? iz - 1 : k == 3 ? iz + 1 : iz, rx = k == 0 ? ix - 1 : k == 1 ? ix + 1 : ix;
-      const int r = g.loc(rz, rx);
-      const long long td0 = AF_XL_DIAG ? clock64() : 0;
-      int path = 0;
-      double v = relax_value(L, M, g, sp, r, rz, rx, ntr, lane, npass, path);
-      const long long td1 = AF_XL_DIAG ? clock64() : 0;
-      if (AF_XL_DIAG) dg[1 + path] += td1 - td0;
-      if (AF_XL_DIAG && path == 1) dg[7]++;
-      if (AF_XL_DIAG && path == 2) dg[8]++;
-      nrel++;
-      if (lane == 0) {
-        if (v == -1.0) {
-          const XField F{L, &g};
-          v = fouds18(F, M, cell_mat(M, g.mv, rz, rx), rz, rx, g.dnx, g.dnz, g.nx, g.nz, mat_slo(M, g.mv, rz, rx));
-        }
-        gst(g.T + (long)rz * g.nx + rx, v);
-        // a far node's new entry is its only one; an updated node's entry says whether it has two
-        if ((fm >> k) & 1ull) h.add(r, v, true);
-        else if (h.upd(r, v)) h.sync(r, v);
-      }
-      v = rlane(v, 0);
-      patch(L, sp, rz, rx, v, lane);
-      ntr = __shfl(h.ntr, 0);
-      if (AF_XL_DIAG) dg[5] += clock64() - td1;
-    }
-  }
-  if (prof && lane == 0) {  // diagnostics: relaxations, evaluation passes (BandSrc::sub)
-    prof[0] += nrel;
-    prof[1] += npass;
-    if (AF_XL_DIAG) {  // BandSrc::ph[0..5] and sub[2..3] (the band kernel writes them only when profiling)
-      for (int k = 0; k < 6; k++) dgo[k] += dg[k];
-      prof[2] += dg[7];
-      prof[3] += dg[8];
-    }
-  }
-  return pops;
-}
-
-// ---- the walk over two wavefronts (AF_XL_TWO_ROLE) ----
+// ---- the heap walk (:2292-2346, :2460-2504, :2775-2817) over two wavefronts ----
+// stage: stop when a popped node's neighbour falls off the stage grid at max_dist + 1 from the
+// source; main grid: stop when the root reaches tstop or comes within 3 nodes of a window edge
+// that is not a grid edge.
 // The heap wavefront pops, classifies the popped node's neighbours (far -> addtree, close ->
-// updtree, read before downtree as in walk()), makes the node known and hands the relaxation jobs
-// to the relax wavefront, then runs downtree while the relaxations are evaluated, and each job's
-// addtree / updtree as soon as its value is posted.  The relax wavefront evaluates the jobs in
-// order (speculative entries / evaluation passes / fouds18_A(), walk()'s relax_value) and stores
-// T.  update() reads T and validity only, which neither downtree nor addtree / updtree change, so
-// the values are walk()'s.  fouds18_A() reads known-ness, which the heap side changes only through
-// a node with two heap entries (setpos makes it close again): while such entries are in the heap
-// (Heap::livedup) the heap runs downtree before posting the jobs and the relax side waits for the
-// earlier jobs' addtree / updtree before a fouds18_A() — the sequential order.
+// updtree, statuses read before downtree as in fmm_exact.hip), makes the node known and hands the
+// relaxation jobs to the relax wavefront, then runs downtree while the relaxations are evaluated,
+// and each job's addtree / updtree as soon as its value is posted.  The relax wavefront evaluates
+// the jobs in order (speculative entries / evaluation passes / fouds18_A(), relax_value) and
+// stores T.  update() reads T and validity only, which neither downtree nor addtree / updtree
+// change, so the values are those of a walk on one wavefront.  fouds18_A() reads known-ness, which
+// the heap side changes only through a node with two heap entries (setpos makes it close again):
+// while such entries are in the heap (Heap::livedup) the heap runs downtree before posting the
+// jobs and the relax side waits for the earlier jobs' addtree / updtree before a fouds18_A() —
+// the sequential order.
 AF_DEV void xpost(int* w, int v) { __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 AF_DEV int xload(int* w) { return __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
-// polls back off with s_sleep(AF_XL_SLEEP) (0: spin)
-#ifndef AF_XL_SLEEP
-#define AF_XL_SLEEP 1
-#endif
+// polls back off with s_sleep
 AF_DEV bool xawait_at_least(int* w, int v) {  // false: timeout (the other role is gone)
   for (long spins = 0; xload(w) < v; spins++) {
-    if (AF_XL_SLEEP) __builtin_amdgcn_s_sleep(AF_XL_SLEEP);
+    __builtin_amdgcn_s_sleep(1);
     if (spins > (1L << 28)) return false;
   }
   return true;
@@ -551,7 +448,7 @@ AF_DEV int xawait_change(int* w, int last) {  // the next value != last, or -2 o
   for (long spins = 0;; spins++) {
     const int v = xload(w);
     if (v != last) return v;
-    if (AF_XL_SLEEP) __builtin_amdgcn_s_sleep(AF_XL_SLEEP);
+    __builtin_amdgcn_s_sleep(1);
     if (spins > (1L << 28)) return -2;
   }
 }
@@ -670,8 +567,7 @@ AF_DEV void relax_role(Lds* L, const DevModel& M, const XG& g, Spec& sp, int lan
       const int jw = q == 0 ? jv.x : q == 1 ? jv.y : q == 2 ? jv.z : jv.w;
       const int r = jw & 0x7fffffff;
       const int rz = g.gz(r), rx = g.gx(r);
-      int path = 0;
-      double v = relax_value(L, M, g, sp, r, rz, rx, ntr, lane, npass, path);
+      double v = relax_value(L, M, g, sp, r, rz, rx, ntr, lane, npass);
       nrel++;
       if (lane == 0) {
         if (v == -1.0) {
@@ -867,33 +763,23 @@ __global__ __launch_bounds__(kThreads) void fmm_exact_lds_kernel(BandParams P) {
     } else if (w0) {
       handover(L, h, pT, pnz, pnx, pisz, pisx, g, isz_s, isx_s, lane);
     }
-    if (AF_XL_TWO_ROLE) {
-      if (tid == 0) {
-        L->cmd = 0;
-        L->done = 0;
-        L->applied = 0;
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // wave 0's grid stores before wave 1 reads them
-      __syncthreads();
-      if (w0) {
-        const long long pops = heap_role(L, h, g, true, isx_s, isz_s, scale * size, 0.0, lane, B->ph);
-        if (lane == 0) {
-          B->steps[stg] = pops;
-          if (h.err) err_s = h.err;
-        }
-      } else if (tid < 128) {
-        relax_role(L, M, g, sp, lane, B->sub, B->ph);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (w0) {
-      sp.c = -1;
-      const long long pops = walk(L, h, M, g, true, isx_s, isz_s, scale * size, 0.0, sp, lane, B->sub, B->ph);
+    if (tid == 0) {
+      L->cmd = 0;
+      L->done = 0;
+      L->applied = 0;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // wave 0's grid stores before wave 1 reads them
+    __syncthreads();
+    if (w0) {
+      const long long pops = heap_role(L, h, g, true, isx_s, isz_s, scale * size, 0.0, lane, B->ph);
       if (lane == 0) {
         B->steps[stg] = pops;
         if (h.err) err_s = h.err;
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else if (tid < 128) {
+      relax_role(L, M, g, sp, lane, B->sub, B->ph);
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     pT = g.T;
     pnz = g.nz;
     pnx = g.nx;
@@ -929,33 +815,23 @@ __global__ __launch_bounds__(kThreads) void fmm_exact_lds_kernel(BandParams P) {
       handover(L, h, pT, pnz, pnx, pisz, pisx, g, (int)isz, (int)isx, lane);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    if (AF_XL_TWO_ROLE) {
-      if (tid == 0) {
-        L->cmd = 0;
-        L->done = 0;
-        L->applied = 0;
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // wave 0's grid stores before wave 1 reads them
-      __syncthreads();
-      if (w0) {
-        const long long pops = heap_role(L, h, g, false, 0, 0, 0, P.tstop, lane, B->ph);
-        if (lane == 0) {
-          B->steps[2] = pops;
-          if (h.err) err_s = h.err;
-        }
-      } else if (tid < 128) {
-        relax_role(L, M, g, sp, lane, B->sub, B->ph);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else if (w0) {
-      sp.c = -1;
-      const long long pops = walk(L, h, M, g, false, 0, 0, 0, P.tstop, sp, lane, B->sub, B->ph);
+    if (tid == 0) {
+      L->cmd = 0;
+      L->done = 0;
+      L->applied = 0;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // wave 0's grid stores before wave 1 reads them
+    __syncthreads();
+    if (w0) {
+      const long long pops = heap_role(L, h, g, false, 0, 0, 0, P.tstop, lane, B->ph);
       if (lane == 0) {
         B->steps[2] = pops;
         if (h.err) err_s = h.err;
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else if (tid < 128) {
+      relax_role(L, M, g, sp, lane, B->sub, B->ph);
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     err = err_s;
   }

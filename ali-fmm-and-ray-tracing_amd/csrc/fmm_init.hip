@@ -33,21 +33,12 @@ constexpr int kInitStab = 64;         // stiffness rows staged in LDS
 #define AF_INIT_DIAG 0
 #endif
 // the heap role runs on its whole wavefront: the pop's neighbour classification spread over the
-// lanes (AF_INIT_PARCLS; 0: one lane's loops).  Its sift-ups and downtree stay one lane's loops:
+// lanes.  Its sift-ups and downtree stay one lane's loops:
 // lane-parallel versions (the ancestors / the min-child path read in one LDS round trip, ballot
 // and readlane chains) and stores deferred to the end of a sift measured slower (profiles/r5d,
-// profiles/r5i_init_deferred_stores_not_kept.txt)
-#ifndef AF_INIT_PARCLS
-#define AF_INIT_PARCLS 1
-#endif
-// the next pop classified and handed to the relax role before the last sift-up of the current
-// one when that sift-up cannot reach the root (stage walks)
-#ifndef AF_INIT_IPARENT
-#define AF_INIT_IPARENT 1
-#endif
-#ifndef AF_INIT_EARLY
-#define AF_INIT_EARLY 1
-#endif
+// profiles/r5i_init_deferred_stores_not_kept.txt).  The next pop is classified and handed to the
+// relax role before the last sift-up of the current one when that sift-up cannot reach the root
+// (stage walks).
 #if AF_INIT_DIAG
 #define AF_DG_T0(v) const long long v = clock64();
 #define AF_DG_ADD(L, k, v) (L)->dg[k] += clock64() - (v);
@@ -107,9 +98,8 @@ struct Heap {
   AF_DEV int bz(int k) const { return L->hcell[k] >> 8; }
   AF_DEV int bx(int k) const { return L->hcell[k] & 255; }
   AF_DEV double tb(int k) const { return L->hkey[k]; }
-  // round(t / 2), half-even (:123), in integer arithmetic (AF_INIT_IPARENT; 0: through a double)
+  // round(t / 2), half-even (:123), in integer arithmetic
   AF_DEV static int parent(int t) {
-    if (!AF_INIT_IPARENT) return (int)rint((double)t / 2.0);
     const int m = t >> 1;
     return (t & 1) ? m + (m & 1) : m;
   }
@@ -296,24 +286,16 @@ AF_DEV int job_pack(int z, int x, int kind) { return (z << 8) | x | (kind << 16)
 AF_DEV void post(int* w, int v) { __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 // the waiting role backs off between polls (s_sleep) so that it does not take issue slots and
 // LDS cycles from the working one
-// the relax role's re-check of a changed speculative entry: lane-parallel stencil stage (1) or
-// one lane (0)
-#ifndef AF_INIT_PARSEL
-#define AF_INIT_PARSEL 1
-#endif
-#ifndef AF_INIT_SLEEP
-#define AF_INIT_SLEEP 1
-#endif
 AF_DEV bool await_value(int* w, int v) {  // false: timeout (the other role is gone)
   for (long spins = 0; __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != v; spins++) {
-    if (AF_INIT_SLEEP) __builtin_amdgcn_s_sleep(AF_INIT_SLEEP);
+    __builtin_amdgcn_s_sleep(1);
     if (spins > (1L << 28)) return false;
   }
   return true;
 }
 AF_DEV bool await_at_least(int* w, int v) {  // false: timeout
   for (long spins = 0; __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < v; spins++) {
-    if (AF_INIT_SLEEP) __builtin_amdgcn_s_sleep(AF_INIT_SLEEP);
+    __builtin_amdgcn_s_sleep(1);
     if (spins > (1L << 28)) return false;
   }
   return true;
@@ -322,7 +304,7 @@ AF_DEV int await_change(int* w, int last) {  // the next value != last, or -2 on
   for (long spins = 0;; spins++) {
     const int v = __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (v != last) return v;
-    if (AF_INIT_SLEEP) __builtin_amdgcn_s_sleep(AF_INIT_SLEEP);
+    __builtin_amdgcn_s_sleep(1);
     if (spins > (1L << 28)) return -2;
   }
 }
@@ -454,7 +436,7 @@ AF_DEV void relax_role(InitLds* L, const DevModel& M, const MatView& mv, const M
           bool vk;
           lane_slot_lds(L->T, L->S, R.z0, R.x0, R.z1, R.x1, R.w, iz, ix, lane, tk, vk);
           UpdSel s2;
-          const bool par = AF_INIT_PARSEL && update_select_lanes(tk, vk, iz, ix, qnnz, R.nnx, lane, s2);
+          const bool par = update_select_lanes(tk, vk, iz, ix, qnnz, R.nnx, lane, s2);
           if (lane == e) {
             if (!par) {
               NbFieldT nb;
@@ -550,50 +532,19 @@ AF_DEV void stage_loop(Heap& h, const DevModel& M, const StageCfg& c, int tid) {
     auto classify = [&](bool& fin) -> int {
       const int ix = h.bx(1), iz = h.bz(1);
       if (tid == 0) L->S[iz * nx + ix] = 0;
-      int n = 0;
-      bool finished = false;
-      if (AF_INIT_PARCLS) {
-        // lane d < 4: neighbour d in the reference's order (x - 1, x + 1, z - 1, z + 1)
-        const int d = tid & 3;
-        const int zz = d < 2 ? iz : (d == 2 ? iz - 1 : iz + 1), xx = d < 2 ? (d == 0 ? ix - 1 : ix + 1) : ix;
-        const bool inb = tid < 4 && (d < 2 ? (0 <= xx && xx <= nx - 1) : (0 <= zz && zz <= nz - 1));
-        const int st = inb ? (int)L->S[zz * nx + xx] : 0;
-        const bool job = inb && (st == -1 || st > 0);
-        const bool out = tid < 4 && !inb && (d < 2 ? abs(c.isx - xx) : abs(c.isz - zz)) == c.max_dist + 1;
-        const unsigned long long jm = __ballot(job);
-        if (__ballot(out)) finished = true;
-        if (job)
-          L->job[__popcll(jm & ((1ull << tid) - 1ull))] =
-              job_pack(zz, xx, st == -1 ? kJobAdd : (kJobUpd | (d < 2 && c.quirk ? kJobQuirk : 0)));
-        n = __popcll(jm);
-      } else {
-        for (int s = 0; s < 2; s++) {
-          const int i = s == 0 ? ix - 1 : ix + 1;
-          if (0 <= i && i <= nx - 1) {
-            const int st = L->S[iz * nx + i];
-            if (st == -1 || st > 0) {
-              L->job[n] = job_pack(iz, i, st == -1 ? kJobAdd : (kJobUpd | (c.quirk ? kJobQuirk : 0)));
-              n++;
-            }
-          } else if (abs(c.isx - i) == c.max_dist + 1) {
-            finished = true;
-          }
-        }
-        for (int s = 0; s < 2; s++) {
-          const int i = s == 0 ? iz - 1 : iz + 1;
-          if (0 <= i && i <= nz - 1) {
-            const int st = L->S[i * nx + ix];
-            if (st == -1 || st > 0) {
-              L->job[n] = job_pack(i, ix, st == -1 ? kJobAdd : kJobUpd);
-              n++;
-            }
-          } else if (abs(c.isz - i) == c.max_dist + 1) {
-            finished = true;
-          }
-        }
-      }
-      fin = finished;
-      return n;
+      // lane d < 4: neighbour d in the reference's order (x - 1, x + 1, z - 1, z + 1)
+      const int d = tid & 3;
+      const int zz = d < 2 ? iz : (d == 2 ? iz - 1 : iz + 1), xx = d < 2 ? (d == 0 ? ix - 1 : ix + 1) : ix;
+      const bool inb = tid < 4 && (d < 2 ? (0 <= xx && xx <= nx - 1) : (0 <= zz && zz <= nz - 1));
+      const int st = inb ? (int)L->S[zz * nx + xx] : 0;
+      const bool job = inb && (st == -1 || st > 0);
+      const bool out = tid < 4 && !inb && (d < 2 ? abs(c.isx - xx) : abs(c.isz - zz)) == c.max_dist + 1;
+      const unsigned long long jm = __ballot(job);
+      fin = __ballot(out) != 0;
+      if (job)
+        L->job[__popcll(jm & ((1ull << tid) - 1ull))] =
+            job_pack(zz, xx, st == -1 ? kJobAdd : (kJobUpd | (d < 2 && c.quirk ? kJobQuirk : 0)));
+      return __popcll(jm);
     };
     // a pop classified (and its jobs handed over) while the previous pop's last sift-up was due
     int pre_n = -1;
@@ -616,7 +567,7 @@ AF_DEV void stage_loop(Heap& h, const DevModel& M, const StageCfg& c, int tid) {
       // first.  The heap operations keep the reference's order (this sift-up, then the next pop's
       // downtree); the next pop's relaxations read ttn and validity only, which sift-ups never touch
       auto early = [&](double key, int cell) {
-        if (!AF_INIT_EARLY || finished || h.err || h.ndup || h.ntr < 1 || key < L->hkey[1] ||
+        if (finished || h.err || h.ndup || h.ntr < 1 || key < L->hkey[1] ||
             (int)L->hcell[1] == cell)
           return;
         bool f2 = false;

@@ -398,11 +398,8 @@ AF_DEV double fouds18(const F& f, const DevModel& M, const CellMat& cm, long iz,
 }
 
 
-// update() index type: grid coordinates fit in int; the long of the reference's numba code
+// update()'s coordinates are int: grid coordinates fit; the long of the reference's numba code
 // only widens the integer arithmetic (the doubles formed from the coordinates are the same)
-#ifndef AF_UPD_IDX
-#define AF_UPD_IDX int
-#endif
 // update()'s triangular-stencil stage (:1146-1366) and its inputs/outputs, shared by the
 // reference-form square stage (update_ref) and the branch-free one for register neighbourhoods
 // (update_nb).  W holds the parameters of the one wavefront_angle_dist() call.
@@ -566,8 +563,8 @@ AF_DEV double upd_finish(const DevModel& M, const CellMat& cm, I ix, I iz, const
 }
 
 template <class F>
-AF_DEV double update_ref(const F& f, const DevModel& M, const CellMat& cm, AF_UPD_IDX iz, AF_UPD_IDX ix, double dnx,
-                     AF_UPD_IDX nnz, AF_UPD_IDX nnx) {
+AF_DEV double update_ref(const F& f, const DevModel& M, const CellMat& cm, int iz, int ix, double dnx,
+                     int nnz, int nnx) {
 #define N_(z, x) f.st((z), (x))
 #define T_(z, x) f.tt((z), (x))
     int sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -604,7 +601,7 @@ AF_DEV double update_ref(const F& f, const DevModel& M, const CellMat& cm, AF_UP
        stencil that the reference's last wavefront_angle_dist call would use (same result, one
        inlined instance instead of 32: keeps the kernels free of register spills) */
     bool have_w = false;
-    AF_UPD_IDX wx1 = 0, wx2 = 0, wx3 = 0, wz1 = 0, wz2 = 0, wz3 = 0;
+    int wx1 = 0, wx2 = 0, wx3 = 0, wz1 = 0, wz2 = 0, wz3 = 0;
     double wy1 = 0, wy2 = 0, wy3 = 0;
 #define SETW(a1, a2, a3, b1, b2, b3, c1, c2, c3) \
     do { wx1 = (a1); wx2 = (a2); wx3 = (a3); wz1 = (b1); wz2 = (b2); wz3 = (b3); \
@@ -688,12 +685,12 @@ AF_DEV double update_ref(const F& f, const DevModel& M, const CellMat& cm, AF_UP
     }
 
     if (sno == -1 || ix == 0 || ix == nnx - 1 || iz == 0 || iz == nnz - 1) {
-        UpdW<AF_UPD_IDX> w{wx1, wx2, wx3, wz1, wz2, wz3, wy1, wy2, wy3, have_w};
+        UpdW<int> w{wx1, wx2, wx3, wz1, wz2, wz3, wy1, wy2, wy3, have_w};
         upd_tri(f, iz, ix, nnz, nnx, sno, min_diff, diff, w, wt, angle, dist);
 #undef SETW
         return upd_finish(M, cm, ix, iz, w, wt, angle, dist, dnx);
     }
-    UpdW<AF_UPD_IDX> w{wx1, wx2, wx3, wz1, wz2, wz3, wy1, wy2, wy3, have_w};
+    UpdW<int> w{wx1, wx2, wx3, wz1, wz2, wz3, wy1, wy2, wy3, have_w};
     return upd_finish(M, cm, ix, iz, w, wt, angle, dist, dnx);
 #undef N_
 #undef T_
@@ -711,7 +708,7 @@ AF_DEV double update_ref(const F& f, const DevModel& M, const CellMat& cm, AF_UP
 // update()'s result is upd_finish() of the stencil stage's outputs: two calls whose stencil
 // stages are equal give the same value (the init kernels' parallel relaxation relies on it)
 struct UpdSel {
-    UpdW<AF_UPD_IDX> w;
+    UpdW<int> w;
     double wt, angle, dist;
     AF_DEV bool same(const UpdSel& o) const {
         return w.have == o.w.have && w.x1 == o.w.x1 && w.x2 == o.w.x2 && w.x3 == o.w.x3 && w.z1 == o.w.z1 &&
@@ -725,8 +722,7 @@ struct UpdSel {
 };
 
 template <class F>
-AF_DEV UpdSel update_nb_select(const F& f, AF_UPD_IDX iz, AF_UPD_IDX ix, AF_UPD_IDX nnz, AF_UPD_IDX nnx) {
-    using I = AF_UPD_IDX;
+AF_DEV UpdSel update_nb_select(const F& f, int iz, int ix, int nnz, int nnx) {
     const bool l1 = ix > 0, l2 = ix > 1, r1 = ix < nnx - 1, r2 = ix < nnx - 2;
     const bool u1 = iz > 0, u2 = iz > 1, d1 = iz < nnz - 1, d2 = iz < nnz - 2;
     const unsigned inb = (l2 ? 1u : 0u) | (l1 ? 2u : 0u) | (r1 ? 4u : 0u) | (r2 ? 8u : 0u) | (u2 ? 16u : 0u) |
@@ -756,7 +752,7 @@ AF_DEV UpdSel update_nb_select(const F& f, AF_UPD_IDX iz, AF_UPD_IDX ix, AF_UPD_
             code = OFF[AP[k]] | (OFF[SA[k]] << 6) | (OFF[SB[k]] << 12);
         }
     }
-    UpdSel r{UpdW<I>{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, false}, 0.0, 0.0, -1.0};
+    UpdSel r{UpdW<int>{0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, false}, 0.0, 0.0, -1.0};
     if (sno >= 0) {
         const bool lo = ya < yb;
         const int pa = (code >> 6) & 63, pb = (code >> 12) & 63;
@@ -801,9 +797,6 @@ AF_DEV double dpp_d(double v) {
     const unsigned lo = (unsigned)dpp_i<CTRL>((int)b), hi = (unsigned)dpp_i<CTRL>((int)(b >> 32));
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
-#ifndef AF_SEL_DPP
-#define AF_SEL_DPP 1
-#endif
 
 // value of lane l (l wave-uniform)
 AF_DEV double lane_d(double v, int l) {
@@ -819,9 +812,8 @@ AF_DEV double lane_d(double v, int l) {
 // stencil, which is the reference's first-minimum scan with strict '<' (:994-1033).  The result is
 // update_nb_select()'s, on every lane.  False (r untouched) where update() runs its triangular
 // stage (a grid-edge cell, or no valid square stencil): the caller then runs update_nb_select().
-AF_DEV bool update_select_lanes(double tk, bool vk, AF_UPD_IDX iz, AF_UPD_IDX ix, AF_UPD_IDX nnz, AF_UPD_IDX nnx,
+AF_DEV bool update_select_lanes(double tk, bool vk, int iz, int ix, int nnz, int nnx,
                                 int lane, UpdSel& r) {
-    using I = AF_UPD_IDX;
     // (>=: stage 1 passes update() its nnx as nnz for close x-neighbours, :1645, so on a grid with
     // more rows than columns a node can lie past the bound; update_nb_select() masks its lower slots)
     if (ix == 0 || ix >= nnx - 1 || iz == 0 || iz >= nnz - 1) return false;
@@ -840,7 +832,6 @@ AF_DEV bool update_select_lanes(double tk, bool vk, AF_UPD_IDX iz, AF_UPD_IDX ix
     const double d = fabs(ta - tb);
     double key = (lane < 8 && (em & msk) == msk && d < 1000000.0) ? d : INFINITY;
     int idx = lane < 8 ? lane : 64;
-#if AF_SEL_DPP
     // lanes 0..7: partners by DPP (quad xor 1, quad xor 2, half-row mirror), no LDS round trip
     auto step = [&](double ok, int oi) {
         if (ok < key || (ok == key && oi < idx)) {
@@ -851,17 +842,6 @@ AF_DEV bool update_select_lanes(double tk, bool vk, AF_UPD_IDX iz, AF_UPD_IDX ix
     step(dpp_d<0xB1>(key), dpp_i<0xB1>(idx));
     step(dpp_d<0x4E>(key), dpp_i<0x4E>(idx));
     step(dpp_d<0x141>(key), dpp_i<0x141>(idx));
-#else
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) {
-        const double ok = __shfl_xor(key, o);
-        const int oi = __shfl_xor(idx, o);
-        if (ok < key || (ok == key && oi < idx)) {
-            key = ok;
-            idx = oi;
-        }
-    }
-#endif
     if (!(lane_d(key, 0) < INFINITY)) return false;
     const int sno = __builtin_amdgcn_readfirstlane(idx);
     const int pa_s = (int)((kSA >> (4 * sno)) & 15u), pb_s = (int)((kSB >> (4 * sno)) & 15u);
@@ -887,21 +867,14 @@ AF_DEV bool update_select_lanes(double tk, bool vk, AF_UPD_IDX iz, AF_UPD_IDX ix
     r.wt = r.w.y2;
     r.angle = 0.0;
     r.dist = -1.0;
-    (void)sizeof(I);
     return true;
 }
 
-// update()'s finish out of line (AF_FINISH_OOL 1, the init and exact-walk kernels): one copy of the
-// wavefront-angle and phase-velocity code per kernel instead of one per call site (measured: init
-// +1 %, subgrid-9 exact walk -1.5 %, profiles/r5t; off).  The arguments
-// are scalars (32 VGPRs: none go through the stack); vp_nc = velpn | ncol << 16 (set_model keeps
-// ncol below 2^15).  Same arithmetic as upd_finish.
-#ifndef AF_FINISH_OOL
-#define AF_FINISH_OOL 0
-#endif
-#if AF_FINISH_OOL
-__attribute__((noinline))
-#endif
+// update()'s finish with scalar arguments, as the init and exact-walk kernels call it: written to
+// go out of line (one copy of the wavefront-angle and phase-velocity code per kernel), which was
+// measured and not kept (init +1 %, subgrid-9 exact walk -1.5 %, profiles/r5t), so it is inlined
+// like upd_finish.  vp_nc = velpn | ncol << 16 (set_model keeps ncol below 2^15).  Same arithmetic
+// as upd_finish.
 AF_DEV double upd_finish_ool(const double* ptab, int vp_nc, double veln, double vm, const double* stif, int ix, int iz,
                              int x1, int x2, int x3, int z1, int z2, int z3, double y1, double y2, double y3, int have,
                              double wt, double angle, double dist, double dnx) {
@@ -917,31 +890,24 @@ AF_DEV double upd_finish_ool(const double* ptab, int vp_nc, double veln, double 
     return -1.0;
 }
 
-AF_DEV double update_nb_finish(const DevModel& M, const CellMat& cm, AF_UPD_IDX iz, AF_UPD_IDX ix, double dnx,
+AF_DEV double update_nb_finish(const DevModel& M, const CellMat& cm, int iz, int ix, double dnx,
                                const UpdSel& r) {
     return upd_finish(M, cm, ix, iz, r.w, r.wt, r.angle, r.dist, dnx);
 }
-// the same through upd_finish_ool (int coordinates)
+// the same through upd_finish_ool
 AF_DEV double update_nb_finish_ool(const DevModel& M, const CellMat& cm, int iz, int ix, double dnx, const UpdSel& r) {
-    static_assert(std::is_same<AF_UPD_IDX, int>::value, "int stencil coordinates");
     return upd_finish_ool(M.ptab, cm.velpn | (M.ncol << 16), cm.veln, cm.vm, cm.stif, ix, iz, r.w.x1, r.w.x2, r.w.x3,
                           r.w.z1, r.w.z2, r.w.z3, r.w.y1, r.w.y2, r.w.y3, r.w.have ? 1 : 0, r.wt, r.angle, r.dist,
                           dnx);
 }
 
 template <class F>
-AF_DEV double update_nb(const F& f, const DevModel& M, const CellMat& cm, AF_UPD_IDX iz, AF_UPD_IDX ix, double dnx,
-                        AF_UPD_IDX nnz, AF_UPD_IDX nnx) {
+AF_DEV double update_nb(const F& f, const DevModel& M, const CellMat& cm, int iz, int ix, double dnx,
+                        int nnz, int nnx) {
     const UpdSel r = update_nb_select(f, iz, ix, nnz, nnx);
-#ifdef AF_UPD_HOOK
-    AF_UPD_HOOK(r.wt + r.angle + r.dist);  // profiling builds: the stencil stage is done
-#endif
     return update_nb_finish(M, cm, iz, ix, dnx, r);
 }
 
-#ifndef AF_UPD_LEAN
-#define AF_UPD_LEAN 1
-#endif
 template <class F, class = void>
 struct upd_regs : std::false_type {};
 template <class F>
@@ -950,9 +916,9 @@ struct upd_regs<F, std::void_t<decltype(&F::t11)>> : std::true_type {};
 // update() (Anis_TTF_rays.py:904-1410): the branch-free form on register neighbourhoods, the
 // reference form on every other field accessor
 template <class F>
-AF_DEV double update(const F& f, const DevModel& M, const CellMat& cm, AF_UPD_IDX iz, AF_UPD_IDX ix, double dnx,
-                     AF_UPD_IDX nnz, AF_UPD_IDX nnx) {
-    if constexpr (AF_UPD_LEAN && upd_regs<F>::value) return update_nb(f, M, cm, iz, ix, dnx, nnz, nnx);
+AF_DEV double update(const F& f, const DevModel& M, const CellMat& cm, int iz, int ix, double dnx,
+                     int nnz, int nnx) {
+    if constexpr (upd_regs<F>::value) return update_nb(f, M, cm, iz, ix, dnx, nnz, nnx);
     else return update_ref(f, M, cm, iz, ix, dnx, nnz, nnx);
 }
 

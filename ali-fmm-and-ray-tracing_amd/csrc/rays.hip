@@ -37,9 +37,7 @@ AF_DEV bool key_less(const Key& a, const Key& b) { return a.v < b.v || (a.v == b
 
 // wavefronts per SIMD the kernel is compiled for (174 VGPRs at 2; 3 or 4 force fewer registers and
 // measured no faster, profiles/r5q; the LDS of a 4-wavefront block also allows two blocks per CU)
-#ifndef AF_RAY_WPE
-#define AF_RAY_WPE 2
-#endif
+constexpr int kRayWpe = 2;
 // Material runs: time_between_points() evaluates the group velocity once per run of pieces in one
 // material; the lanes of a wavefront reach their runs' evaluations at different pieces, so the
 // one-lane loop re-issues the evaluation for every piece index at which any lane changes material.
@@ -48,41 +46,23 @@ AF_DEV bool key_less(const Key& a, const Key& b) { return a.v < b.v || (a.v == b
 // evaluation per lane), then sums the pieces in the reference's order (segments longer than the
 // kept pieces walk again).  The same values: a run's slowness depends on its material record and
 // the segment's angle only.
-#ifndef AF_RAY_BATCH
-#define AF_RAY_BATCH 1
-#endif
-// material ids of a segment's first pieces read ahead of the run scan (0: one read per piece)
-#ifndef AF_RAY_PF
-#define AF_RAY_PF 8
-#endif
+constexpr int kPf = 8;    // material ids of a segment's first pieces read ahead of the run scan
 constexpr int kRuns = 4;  // runs per segment handled this way (more: the one-lane loop)
 // piece lengths kept from the first walk for the summing one (segments of more pieces walk again)
-#ifndef AF_RAY_PC
-#define AF_RAY_PC 12
-#endif
-constexpr int kPc = AF_RAY_PC;
+constexpr int kPc = 12;
 struct RayScratch {  // per wavefront
   double slo[64 * kRuns];
   double ang[64];
   int item[64 * kRuns];
-  double dist[64 * (kPc > 0 ? kPc : 1)];  // piece k of lane l: dist[64 k + l]
+  double dist[64 * kPc];  // piece k of lane l: dist[64 k + l]
 };
 
 // the group-velocity evaluation, one copy in the kernel: inlined at every call site the kernel's
-// code was 131 KB, out of line 18 + 27 KB at the same speed (profiles/r5q; AF_RAY_SLO_NOINLINE 0:
-// inlined)
-#ifndef AF_RAY_SLO_NOINLINE
-#define AF_RAY_SLO_NOINLINE 1
-#endif
-#if AF_RAY_SLO_NOINLINE
+// code was 131 KB, out of line 18 + 27 KB at the same speed (profiles/r5q)
 __attribute__((noinline))
-#endif
 AF_DEV double ray_slowness(double veln, double vm, int velpn, const double* stif, double angle, const double* gtab,
                            int ncol) {
   // tbp_slowness / group_vel_cell with the record's fields
-#ifdef AF_RAY_DIAG_SLO  // diagnostic build only (wrong rays): the kernel without the evaluations
-  return 1.0 / (vm + 1e-9 * angle + 1e-12 * veln);
-#endif
   const double eff = pymod(veln - angle, 180);
   const double velocity =
       (velpn != 0 || stif == nullptr) ? table_vel(gtab, ncol, eff, velpn, vm) : christoffel_group(stif, eff, vm);
@@ -116,13 +96,13 @@ AF_DEV double tbp_wave(const DevModel& M, const MatLds& ms, RayScratch& S, bool 
       }
     };
     int k = 0;
-    if constexpr (AF_RAY_PF > 0) {
-      // the first AF_RAY_PF pieces' material ids: reads issued together (the walk's geometry does
+    {
+      // the first kPf pieces' material ids: reads issued together (the walk's geometry does
       // not depend on them), one memory latency instead of one per piece
-      int idv[AF_RAY_PF > 0 ? AF_RAY_PF : 1];
+      int idv[kPf];
       int npf = 0;
 #pragma unroll
-      for (int q = 0; q < AF_RAY_PF; q++) {
+      for (int q = 0; q < kPf; q++) {
         idv[q] = 0;
         if (!w.done()) {
           double nxv, nyv;
@@ -137,7 +117,7 @@ AF_DEV double tbp_wave(const DevModel& M, const MatLds& ms, RayScratch& S, bool 
         }
       }
 #pragma unroll
-      for (int q = 0; q < AF_RAY_PF; q++)
+      for (int q = 0; q < kPf; q++)
         if (q < npf) run(q, idv[q]);
       k = npf;
     }
@@ -175,14 +155,7 @@ AF_DEV double tbp_wave(const DevModel& M, const MatLds& ms, RayScratch& S, bool 
     if (j < ntot) {
       const int it = S.item[j];
       const int l = it >> 10, r = (it >> 8) & 3, id = it & 255;
-#ifdef AF_RAY_DIAG_DBL  // diagnostic build: every evaluation twice (its marginal cost), same results
-      double a2 = S.ang[l];
-      asm volatile("" : "+v"(a2));
-      const double s2 = ray_slowness(M, ms, id, a2);
-      S.slo[l * kRuns + r] = ray_slowness(M, ms, id, S.ang[l]) + (s2 == -12345.0 ? 1.0 : 0.0);
-#else
       S.slo[l * kRuns + r] = ray_slowness(M, ms, id, S.ang[l]);
-#endif
     }
   }
   __builtin_amdgcn_wave_barrier();
@@ -228,7 +201,7 @@ AF_DEV double tbp_wave(const DevModel& M, const MatLds& ms, RayScratch& S, bool 
 }
 
 template <int G, bool LDSMAT>
-__global__ __launch_bounds__(64 * kRayWaves) __attribute__((amdgpu_waves_per_eu(AF_RAY_WPE))) void find_ray_kernel(
+__global__ __launch_bounds__(64 * kRayWaves) __attribute__((amdgpu_waves_per_eu(kRayWpe))) void find_ray_kernel(
     RayParams P) {
   constexpr int kGroups = 64 / G;             // rays per wavefront
   constexpr int kTT = kMaxCand / kGroups;      // candidate slots per ray
@@ -237,7 +210,7 @@ __global__ __launch_bounds__(64 * kRayWaves) __attribute__((amdgpu_waves_per_eu(
   __shared__ MatRec smat[LDSMAT ? kRayMatLds : 1];
   __shared__ double sstab[LDSMAT ? 5 * kRayStabLds : 1];
   __shared__ double sgtab[LDSMAT ? kRayGtabLds : 1];
-  __shared__ RayScratch RS[LDSMAT && AF_RAY_BATCH ? kRayWaves : 1];
+  __shared__ RayScratch RS[LDSMAT ? kRayWaves : 1];
   crm::lds_init();
   if (LDSMAT) {
     for (int k = threadIdx.x; k < P.M.nmat; k += blockDim.x) smat[k] = P.M.mtab[k];
@@ -362,7 +335,7 @@ __global__ __launch_bounds__(64 * kRayWaves) __attribute__((amdgpu_waves_per_eu(
       }
       const double rt = ok ? RT(ya, xa) : 0.0;
       double tb;
-      if constexpr (LDSMAT && AF_RAY_BATCH) {
+      if constexpr (LDSMAT) {
         tb = tbp_wave(P.M, ms, RS[w], ok, last_x, (double)xa, last_y, (double)ya, P.dnx, sg, wl);
       } else {
         tb = ok ? tbp(P.M, ms, last_x, (double)xa, last_y, (double)ya, P.dnx, sg) : 0.0;
@@ -471,15 +444,11 @@ __global__ __launch_bounds__(64 * kRayWaves) __attribute__((amdgpu_waves_per_eu(
   // reference's strict '<' never sets fin_y, and the walk runs off the grid without end; rays that
   // circle on a flat field until the capacity hold such segments.
   const bool timed = !(flags & 6);
-#ifdef AF_RAY_DIAG_NOTIME  // diagnostic build only (no ray times): the walk alone
-  for (long k0 = 0; k0 < 0; k0 += G) {
-#else
   for (long k0 = 0; timed && k0 < npts - 1; k0 += G) {
-#endif
     const long k = k0 + lane;
     const bool ok = k < npts - 1;
     double seg = 0.0;
-    if constexpr (LDSMAT && AF_RAY_BATCH) {
+    if constexpr (LDSMAT) {
       const double xa = ok ? gld(rxo + k) : 0.0, xb = ok ? gld(rxo + k + 1) : 0.0;
       const double ya = ok ? gld(ryo + k) : 0.0, yb = ok ? gld(ryo + k + 1) : 0.0;
       seg = tbp_wave(P.M, ms, RS[w], ok, xa, xb, ya, yb, P.dnx, sg, wl);
@@ -519,23 +488,15 @@ extern "C" hipError_t af_launch_pack_rays(const double* rx, const double* ry, co
   return hipGetLastError();
 }
 
-extern "C" int af_ray_waves_per_simd() { return AF_RAY_WPE; }
+extern "C" int af_ray_waves_per_simd() { return af::kRayWpe; }
 
-// lanes per ray (a power of two): candidates of one search plane across lanes; AF_RAY_GMIN 8 puts
-// 8 rays in a wavefront at subgrid 1 (9 axis-plane candidates then take two rounds)
-// subgrid 1: groups of exactly the 9 candidates (1) instead of 16 lanes (0)
-#ifndef AF_RAY_G9
-#define AF_RAY_G9 1
-#endif
-#ifndef AF_RAY_GMIN
-#define AF_RAY_GMIN 16
-#endif
+// lanes per ray (a power of two, at least 16, or 9): candidates of one search plane across lanes.
 // packed: the launch has rays enough to fill the device at 7 rays per wavefront (9-lane groups at
 // subgrid 1); else 16 lanes (4 rays per wavefront: twice the wavefronts for a smaller launch)
 extern "C" int af_ray_group_lanes(int sg, int packed) {
   const int ncand = 6 * sg + 3;  // axis planes; diagonal planes have <= 5*sg+3
-  if (AF_RAY_G9 && packed && ncand == 9) return 9;  // subgrid 1: 7 rays of 9 lanes per wavefront
-  return ncand <= AF_RAY_GMIN ? AF_RAY_GMIN : ncand <= 16 ? 16 : ncand <= 32 ? 32 : 64;
+  if (packed && ncand == 9) return 9;  // subgrid 1: 7 rays of 9 lanes per wavefront
+  return ncand <= 16 ? 16 : ncand <= 32 ? 32 : 64;
 }
 
 extern "C" hipError_t af_launch_rays(const af::RayParams* P, hipStream_t stream) {

@@ -356,3 +356,25 @@ def test_bench_refuses_more_gpus_than_visible():
     assert r.returncode == 2, (r.returncode, r.stderr[-2000:])
     assert "GPU(s) visible" in r.stderr
 
+
+
+def test_build_switches_stay_retired():
+    """The kernels carry three build switches and no more: the two hand-built diagnostic libraries
+    (tools/init_diag.py, tools/exact_lds_diag.py) and the math-library selection.  A measured
+    constant is a constexpr and a decided experiment's other arm lives in the git history
+    (DESIGN.md §7), so a new `#ifndef AF_*` / `#ifdef AF_*` in csrc/ fails here; the band kernel has
+    no preprocessor conditional at all."""
+    import glob
+
+    allowed = {"AF_INIT_DIAG", "AF_XL_DIAG", "AF_CRMATH"}
+    csrc = os.path.join(REPO, "ali-fmm-and-ray-tracing_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) >= 15, files
+    found = {}
+    for f in files:
+        for name in re.findall(r"^\s*#\s*ifn?def\s+(AF_\w+)", open(f).read(), flags=re.M):
+            found.setdefault(name, os.path.basename(f))
+    assert set(found) <= allowed, {n: f for n, f in found.items() if n not in allowed}
+    assert set(found) == allowed, found  # (the scan itself still sees the three that exist)
+    band = open(os.path.join(csrc, "fmm_band_k.hip")).read()
+    assert not re.findall(r"^\s*#\s*(?:if|ifdef|ifndef)\b.*", band, flags=re.M)

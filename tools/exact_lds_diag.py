@@ -1,7 +1,7 @@
 """Cycle split of the LDS exact walk (diagnostic build AF_XL_DIAG=1, GPU box): weld example, 31
-bottom receivers at subgrid 9; per source 0: shader-clock cycles of pop, relaxation value by path
-(clean speculative entry / stencil stage unchanged / finish on the entry's lane / evaluation pass)
-and commit, with the path counts -> one JSON line.
+bottom receivers at subgrid 9; per source 0: shader-clock cycles of the heap wavefront (waits for
+relaxations, downtree, addtree / updtree, the rest) and the relax wavefront (waits for a command,
+work) -> one JSON line.
 ALIFMM_LIB=variants/xdiag/libalifmm.so python tools/exact_lds_diag.py"""
 import json
 import os
@@ -24,13 +24,8 @@ init_ms = ctx.last_timing()[0]
 bp = ctx.band_profile(0).astype(float)
 steps = ctx.source_stats(0)[0]
 pops = float(steps[0] + steps[1] + steps[2])
-two_role = ctx.get_option("exact_lds") == 1 and os.environ.get("AF_XL_ONE_WAVE") is None
-if two_role:  # heap_role / relax_role timers (the default build: AF_XL_TWO_ROLE)
-    names = ["heap_wait_relax", "heap_downtree", "heap_add_upd", "heap_classify_rest", "relax_wait_cmd",
-             "relax_work"]
-else:
-    names = ["pop", "entry_clean", "entry_same_stage", "entry_finish", "eval_pass", "commit"]
-out = {"fields": len(rx), "subgrid": 9, "init_ms": init_ms, "pops_src0": pops, "two_role": two_role,
+names = ["heap_wait_relax", "heap_downtree", "heap_add_upd", "heap_classify_rest", "relax_wait_cmd", "relax_work"]
+out = {"fields": len(rx), "subgrid": 9, "init_ms": init_ms, "pops_src0": pops,
        "relaxations_src0": bp[10], "passes_src0": bp[11],
        "cycles_per_pop": {n: round(bp[k] / pops, 1) for k, n in enumerate(names)}}
 print(json.dumps(out))

@@ -15,7 +15,9 @@ import _alifmm  # noqa: E402
 import workloads as W  # noqa: E402
 
 PH = ["p1_x1", "accept_rim", "claim", "evaluate", "fallback", "commit"]
-SUB = ["x1_wait", "rim_read", "dedupe", "drain"]
+# BandSrc::sub: [X1 wait, rim read, XCD-local steps x 100, drain before X1]; with the / 100 / steps
+# below the third is the fraction of steps whose exchange was XCD-local
+SUB = ["x1_wait", "rim_read", "xcd_local_frac", "drain"]
 
 
 def main():
@@ -51,7 +53,7 @@ def main():
         prof.update({k: round(p[10 + i] / 100.0 / st, 2) for i, k in enumerate(SUB)})
         # list sizes of member 0: mean live close set, accepted and claimed cells per step, max close-set high-water
         prof.update({"live_mean": round(p[6] / st, 1), "acc_mean": round(p[7] / st, 1), "claimed_mean": round(p[8] / st, 1),
-                     "close_hi_max": int(p[9]), "sub3_raw": int(p[13]), "steps": st})
+                     "close_hi_max": int(p[9]), "steps": st})
         out[str(ns)] = {"k": int(ctx.get_option("last_k")), "band_ms": round(best, 1), "init_ms": round(ti, 1),
                         "fields": h.hexdigest()[:16], "span": span, "us_per_step": prof}
     print(json.dumps(out), flush=True)

@@ -78,8 +78,8 @@ def main():
         st = int(ctx.source_stats(0)[0][3])
         names = ["p1_x1", "accept_rim", "claim", "evaluate", "fallback", "commit"]
         r = {n: p[i] / 100.0 / st for i, n in enumerate(names)}
-        r.update({"x1_wait": p[10] / 100.0 / st, "rim_read": p[11] / 100.0 / st, "dedupe": p[12] / 100.0 / st,
-                  "claim_loads": p[13] / 100.0 / st, "close_mean": p[6] / st, "acc_mean": p[7] / st,
+        r.update({"x1_wait": p[10] / 100.0 / st, "rim_read": p[11] / 100.0 / st, "xcd_local_frac": p[12] / 100.0 / st,
+                  "drain": p[13] / 100.0 / st, "close_mean": p[6] / st, "acc_mean": p[7] / st,
                   "eval_mean": p[8] / st, "steps": st, "k": ctx.get_option("last_k")})
         out["prof_%d" % ns] = r
         print(json.dumps({"prof_%d" % ns: r}), flush=True)
