@@ -770,6 +770,7 @@ class ALI_FMM:
         if save_rays:
             self.rays = store
             self.ray_len = store.ray_len
+            self._ray_model = (veln, velpn, vel_map, stif_den)  # what ray_sensitivity() walks the rays on
             if n_trans * n_trans * max_pts * 8 <= ray_dense_limit_bytes:
                 self.ray_paths_x = store.dense(0)
                 self.ray_paths_y = store.dense(1)
@@ -811,6 +812,52 @@ class ALI_FMM:
             return x.copy(), z.copy()
         ray_len = self.ray_len[i, j]
         return self.ray_paths_x[i, j, 0:ray_len], self.ray_paths_y[i, j, 0:ray_len]
+
+    def ray_sensitivity(self, weights=None, pairs=None, rows=False):
+        """Travel-time sensitivities along the rays of the last find_all_TTF_rays* call (not in the
+        reference, which stops at slown_d_slown_stif :3468 and travel_times :3026): what a
+        time-of-flight inversion for the orientation map or a velocity map needs per iteration,
+        computed on the GPU (alifmm_ray_sens) on the model those rays were traced on.
+
+        weights: (n, n) array, weights[i, j] the weight of ray (i, j) in the maps (e.g. the time
+        residuals: the third map is then the misfit gradient in the orientation); None: 1.
+        pairs: the rays to take, a sequence of (i, j); None: every traced ray, row-major.
+        Returns maps (3, nnz, nnx): per coarse cell the sums over the rays of w * length [m],
+        w * time [s] (d t / d vel_map[c] = -time_c / vel_map[c]) and w * d time / d veln [s / degree].
+        rows=True: (maps, (row_ptr, col, len, time, dth), pairs), the unmerged CSR rows of the
+        Jacobian, one row per ray of `pairs` ((m, 2) array), col = iz * nnx + ix.
+        The store holds coordinates on the model grid, so they are walked with subgrid 1:
+        time_between_points() divides by the subgrid first, so the bits are those of the fine
+        coordinates.  One GPU; maps of several GPUs add on the host."""
+        if getattr(self, "rays", None) is None:
+            raise ValueError("no rays: call find_all_TTF_rays* with save_rays=True first")
+        store = self.rays
+        if pairs is None:
+            ii, jj = np.nonzero(store.ray_len)
+        else:
+            pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+            ii, jj = pairs[:, 0], pairs[:, 1]
+        lens = store.ray_len[ii, jj].astype(np.int64)
+        offs = store.ray_off[ii, jj]
+        total = int(lens.sum())
+        # row of every point in the store: ray k's points are offs[k] .. offs[k] + lens[k] - 1
+        idx = np.repeat(offs - (np.cumsum(lens) - lens), lens) + np.arange(total)
+        pts = store.points[idx]
+        w = None
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            if weights.shape != store.ray_len.shape:
+                raise ValueError("weights must have shape (n, n)")
+            w = weights[ii, jj]
+        veln, velpn, vel_map, stif_den = self._ray_model
+        mtab = (veln, velpn, vel_map, stif_den, self.velocity_dat, self.phase_vel)
+        ctx = self._ctx(0)
+        _load_model(ctx, *mtab, self.dnx, self.dnz, self.gox, self.goz,
+                    key=_model_key(*mtab, self.dnx, self.dnz, self.gox, self.goz))
+        maps, csr, _ = ctx.ray_sens(lens, pts, subgrid=1, weights=w, maps=True, rows=rows)
+        if not rows:
+            return maps
+        return maps, csr, np.stack([ii, jj], axis=1)
 
     def save_ray_store(self, path):
         """Write the last call's rays in the compact layout (raystore.RayStore.save: ray_len,

@@ -81,6 +81,7 @@ def _load():
             "alifmm_init_profile": (_i, [_p, _i, _p]),
             "alifmm_put_field": (_i, [_p, _i, _i, _p]),
             "alifmm_tfm": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
+            "alifmm_ray_sens": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p]),
             "alifmm_time_between_points": (_i, [_p, _i, _p, _p, _p, _p, _i, _p]),
             "alifmm_local_ops": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i,
                                       _p]),
@@ -421,6 +422,48 @@ class Context:
             rays.append((p[:, 0].copy(), p[:, 1].copy()))
             off += lens[k]
         return times, lens, flags, rays
+
+    def ray_sens(self, ray_len, ray_xy=None, subgrid=1, flags=None, weights=None, maps=True, rows=False):
+        """Travel-time sensitivities along rays (alifmm_ray_sens): per piece of every ray the coarse
+        cell, the length [m], the time [s] and the time's derivative in the cell's orientation
+        [s / degree].
+
+        ray_len: points per ray; ray_xy: their packed (sum(ray_len), 2) points on the fine grid of
+        `subgrid`, or None for the points the last find_rays kept on the device
+        (alifmm_find_rays(..., NULL, ALIFMM_KEEP_RAYS)); flags: find_rays' flags (rays cut short are
+        skipped); weights: per-ray weights of the maps.
+        Returns (maps, csr, status): maps (3, nnz, nnx) = sums of w len, w time, w dth per cell, or
+        None; csr = (row_ptr, col, len, time, dth) with rows=True, or None; status: 1 for an invalid
+        ray (a non-finite point, a cell outside the grid, an unending segment), which has no entries."""
+        lens = _ci32(np.atleast_1d(ray_len))
+        n = len(lens)
+        xy = None
+        if ray_xy is not None:
+            xy = _c64(ray_xy).reshape(-1, 2)
+            if len(xy) != int(np.maximum(lens, 0).sum(dtype=np.int64)):
+                raise ValueError("ray_xy holds %d points, ray_len adds up to %d"
+                                 % (len(xy), int(np.maximum(lens, 0).sum(dtype=np.int64))))
+        fl = None if flags is None else _ci32(np.atleast_1d(flags))
+        w = None if weights is None else _c64(np.atleast_1d(weights))
+        if (fl is not None and len(fl) != n) or (w is not None and len(w) != n):
+            raise ValueError("flags and weights must have one value per ray")
+        status = np.zeros(n, dtype=np.int32)
+        L = lib()
+
+        def call(m, rp, cap, arrays):
+            self._chk(L.alifmm_ray_sens(self._h, int(subgrid), n, _ptr(lens), _ptr(fl), _ptr(xy), _ptr(w), _ptr(m),
+                                        _ptr(rp), cap, *[_ptr(a) for a in arrays], _ptr(status)), "ray_sens")
+
+        m = np.empty((3,) + tuple(self.shape)) if maps else None
+        if not rows:
+            call(m, None, 0, (None, None, None, None))
+            return m, None, status
+        row_ptr = np.zeros(n + 1, dtype=np.int64)
+        call(None, row_ptr, 0, (None, None, None, None))  # the count pass
+        cap = int(row_ptr[n])
+        arrays = (np.empty(cap, dtype=np.int32), np.empty(cap), np.empty(cap), np.empty(cap))
+        call(m, row_ptr, cap, arrays)
+        return m, (row_ptr,) + arrays, status
 
     def source_stats(self, slot):
         steps = np.zeros(4, dtype=np.int64)

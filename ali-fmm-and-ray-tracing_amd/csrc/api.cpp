@@ -264,6 +264,12 @@ int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   free_ray_bufs(ctx);
   dfree(ctx->tfm.fmc); dfree(ctx->tfm.w); dfree(ctx->tfm.tab); dfree(ctx->tfm.img);
   ctx->tfm = alifmm_ctx::TfmBufs();
+  {
+    auto& b = ctx->sens;
+    dfree(b.xy); dfree(b.off); dfree(b.cnt); dfree(b.row); dfree(b.len); dfree(b.flags); dfree(b.status); dfree(b.w);
+    dfree(b.maps);
+    b = alifmm_ctx::SensBufs();
+  }
   for (int b = 0; b < alifmm_ctx::kPinBufs; b++) {
     if (ctx->pin[b]) (void)hipHostFree(ctx->pin[b]);
     if (ctx->pin_ev[b]) (void)hipEventDestroy(ctx->pin_ev[b]);
@@ -344,6 +350,11 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "tfm_upload_ms")) *value = ctx->t_tfm_upload;
   else if (!strcmp(name, "tfm_kernel_ms")) *value = ctx->t_tfm_kernel;
   else if (!strcmp(name, "tfm_chunk")) *value = ctx->tfm_chunk;
+  // last alifmm_ray_sens call: host -> device copies (host clock, ms), the count and fill kernels
+  // (HIP events, ms), the entries (row_ptr[nrays])
+  else if (!strcmp(name, "sens_upload_ms")) *value = ctx->t_sens_upload;
+  else if (!strcmp(name, "sens_kernel_ms")) *value = ctx->t_sens_kernel;
+  else if (!strcmp(name, "sens_entries")) *value = (double)ctx->sens_entries;
   else return fail(ctx, ALIFMM_E_ARG, "unknown option: %s", name);
   return ALIFMM_OK;
 }
@@ -1685,6 +1696,191 @@ int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, in
   ctx->t_tfm_kernel = ms;
   HIPCHK(hipMemcpy(image, B.img, nimg * sizeof(double), hipMemcpyDeviceToHost));
   return ALIFMM_OK;
+}
+
+int alifmm_ray_sens(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_len, const int32_t* flags,
+                    const double* ray_xy, const double* ray_w, double* maps, int64_t* row_ptr, int64_t cap,
+                    int32_t* col, double* len, double* time, double* dth, int32_t* ray_status) {
+  if (!ctx) return ALIFMM_E_ARG;
+  if (!ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "ray_sens: no model");
+  if (subgrid < 1) return fail(ctx, ALIFMM_E_ARG, "ray_sens: subgrid %d", subgrid);
+  if (nrays < 0) return fail(ctx, ALIFMM_E_ARG, "ray_sens: nrays %d", nrays);
+  if (!ray_len) return fail(ctx, ALIFMM_E_ARG, "ray_sens: ray_len is NULL");
+  const bool want_rows = col || len || time || dth;
+  if (!maps && !row_ptr && !want_rows && !ray_status)
+    return fail(ctx, ALIFMM_E_ARG, "ray_sens: nothing requested (maps, row_ptr and ray_status are NULL)");
+  if (want_rows && !row_ptr) return fail(ctx, ALIFMM_E_ARG, "ray_sens: row arrays without row_ptr");
+  // the rays' first points; a length below 0 counts as no points
+  std::vector<long long> off((size_t)nrays + 1, 0);
+  for (int k = 0; k < nrays; k++) off[k + 1] = off[k] + std::max(ray_len[k], 0);
+  const long long npts = off[nrays];
+  // chunks of whole rays whose points are on the device together: [first ray, end ray), device
+  // pointer (kept points) or null (host points, uploaded into the context's buffer)
+  struct Chunk {
+    int r0, r1;
+    const double* d;
+  };
+  std::vector<Chunk> chunks;
+  if (!ray_xy) {
+    if (!ctx->kept_rays.empty())
+      return fail(ctx, ALIFMM_E_ARG, "ray_sens: the kept rays are staged on the host (several subgrids in one "
+                                     "find_rays call); pass their points as ray_xy");
+    if (npts != ctx->kept_pts)
+      return fail(ctx, ALIFMM_E_ARG, "ray_sens: ray_len adds up to %lld points, %lld are kept", npts,
+                  (long long)ctx->kept_pts);
+    int r = 0;
+    for (auto& k : ctx->kept_dev) {
+      const long long end = off[r] + k.npts;
+      int r1 = r;
+      while (r1 < nrays && off[r1 + 1] <= end) r1++;
+      if (off[r1] != end) return fail(ctx, ALIFMM_E_ARG, "ray_sens: ray_len does not match the kept rays");
+      if (r1 > r) chunks.push_back({r, r1, k.d});
+      r = r1;
+    }
+    if (r != nrays && off[r] != npts) return fail(ctx, ALIFMM_E_ARG, "ray_sens: ray_len does not match the kept rays");
+  } else {
+    const long long kChunkPts = 1LL << 24;  // 256 MB of points per upload (a longer ray is a chunk of its own)
+    for (int r = 0; r < nrays;) {
+      int r1 = r + 1;
+      while (r1 < nrays && off[r1 + 1] - off[r] <= kChunkPts) r1++;
+      chunks.push_back({r, r1, nullptr});
+      r = r1;
+    }
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  alifmm_ctx::SensBufs& B = ctx->sens;
+  const size_t nr = (size_t)nrays, ncell = (size_t)ctx->nz0 * ctx->nx0;
+  ctx->t_sens_upload = ctx->t_sens_kernel = 0;
+  ctx->sens_entries = 0;
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto ms_since = [&](std::chrono::steady_clock::time_point t) {
+    return std::chrono::duration<double, std::milli>(now() - t).count();
+  };
+  HIPCHK(dgrow(&B.off, &B.off_n, nr));
+  HIPCHK(dgrow(&B.len, &B.len_n, nr));
+  HIPCHK(dgrow(&B.cnt, &B.cnt_n, nr));
+  HIPCHK(dgrow(&B.status, &B.status_n, nr));
+  if (flags) HIPCHK(dgrow(&B.flags, &B.flags_n, nr));
+  if (ray_w) HIPCHK(dgrow(&B.w, &B.w_n, nr));
+  {
+    const auto t0 = now();
+    if (nrays) {
+      HIPCHK(hipMemcpy(B.off, off.data(), nr * 8, hipMemcpyHostToDevice));
+      HIPCHK(hipMemcpy(B.len, ray_len, nr * 4, hipMemcpyHostToDevice));
+      if (flags) HIPCHK(hipMemcpy(B.flags, flags, nr * 4, hipMemcpyHostToDevice));
+      if (ray_w) HIPCHK(hipMemcpy(B.w, ray_w, nr * 8, hipMemcpyHostToDevice));
+    }
+    ctx->t_sens_upload += ms_since(t0);
+  }
+  af::SensParams P;
+  memset(&P, 0, sizeof P);
+  P.M = dev_model(ctx);
+  P.sg = subgrid;
+  P.dnx = ctx->dnx;
+  P.off = B.off;
+  P.len = B.len;
+  P.flags = flags ? B.flags : nullptr;
+  P.w = ray_w ? B.w : nullptr;
+  P.cnt = B.cnt;
+  P.status = B.status;
+  int resident = -1;  // the host chunk whose points the context's buffer holds
+  // the chunk's points on the device, then one pass (count or fill) over its rays
+  auto run_chunk = [&](int ci, bool fill) -> int {
+    const Chunk& c = chunks[ci];
+    const long long n = off[c.r1] - off[c.r0];
+    if (c.d) {
+      P.xy = c.d;
+    } else {
+      if (resident != ci) {
+        HIPCHK(dgrow(&B.xy, &B.xy_n, (size_t)2 * std::max<long long>(n, 1)));
+        const auto t0 = now();
+        if (n) HIPCHK(hipMemcpy(B.xy, ray_xy + 2 * off[c.r0], (size_t)n * 16, hipMemcpyHostToDevice));
+        ctx->t_sens_upload += ms_since(t0);
+        resident = ci;
+      }
+      P.xy = B.xy;
+    }
+    P.pt0 = off[c.r0];
+    P.ray0 = c.r0;
+    P.nrays = c.r1 - c.r0;
+    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+    HIPCHK(fill ? af_launch_sens_fill(&P, ctx->stream) : af_launch_sens_count(&P, ctx->stream));
+    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    ctx->t_sens_kernel += ms;
+    return ALIFMM_OK;
+  };
+  int rc = ALIFMM_OK;
+  for (int ci = 0; ci < (int)chunks.size(); ci++)
+    if ((rc = run_chunk(ci, false))) return rc;
+  // row offsets (rays outside every chunk have no points: no entries, status 0)
+  std::vector<long long> rows(nr + 1, 0);
+  std::vector<int32_t> status(nr, 0);
+  {
+    std::vector<long long> cnt(nr, 0);
+    for (const Chunk& c : chunks) {
+      HIPCHK(hipMemcpy(cnt.data() + c.r0, B.cnt + c.r0, (size_t)(c.r1 - c.r0) * 8, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(status.data() + c.r0, B.status + c.r0, (size_t)(c.r1 - c.r0) * 4, hipMemcpyDeviceToHost));
+    }
+    for (size_t k = 0; k < nr; k++) rows[k + 1] = rows[k] + cnt[k];
+  }
+  const long long total = rows[nr];
+  ctx->sens_entries = total;
+  if (row_ptr)
+    for (size_t k = 0; k <= nr; k++) row_ptr[k] = rows[k];
+  if (ray_status && nrays) memcpy(ray_status, status.data(), nr * 4);
+  if (want_rows && cap < total)
+    return fail(ctx, ALIFMM_E_ARG, "ray_sens: cap %lld < %lld entries (row_ptr holds the sizes)", (long long)cap, total);
+  if (!maps && !want_rows) return ALIFMM_OK;
+  // the fill pass: maps in the context's buffer, rows in buffers of this call
+  int32_t* d_col = nullptr;
+  double* d_e[3] = {nullptr, nullptr, nullptr};
+  auto cleanup = [&] {
+    dfree(d_col);
+    for (double* p : d_e) dfree(p);
+  };
+  double* const h_e[3] = {len, time, dth};
+  hipError_t e = hipSuccess;
+  if (maps) {
+    e = dgrow(&B.maps, &B.maps_n, 3 * ncell);
+    if (e == hipSuccess) e = hipMemsetAsync(B.maps, 0, 3 * ncell * 8, ctx->stream);
+  }
+  if (want_rows && total > 0) {
+    if (e == hipSuccess) e = dgrow(&B.row, &B.row_n, nr);
+    if (e == hipSuccess) e = hipMemcpy(B.row, rows.data(), nr * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && col) e = dalloc(&d_col, (size_t)total);
+    for (int q = 0; q < 3; q++)
+      if (e == hipSuccess && h_e[q]) e = dalloc(&d_e[q], (size_t)total);
+  }
+  if (e != hipSuccess) {
+    cleanup();
+    return fail(ctx, ALIFMM_E_HIP, "ray_sens: %s", hipGetErrorString(e));
+  }
+  P.maps = maps ? B.maps : nullptr;
+  if (want_rows && total > 0) {
+    P.row = B.row;
+    P.col = d_col;
+    P.elen = d_e[0];
+    P.etime = d_e[1];
+    P.edth = d_e[2];
+  }
+  if (total > 0 && (maps || P.row))
+    for (int ci = 0; ci < (int)chunks.size() && !rc; ci++) rc = run_chunk(ci, true);
+  if (!rc && maps) {
+    std::vector<D2HSeg> segs{{(const char*)B.maps, (char*)maps, 3 * ncell * 8}};
+    rc = d2h_pageable(ctx, segs);
+  }
+  if (!rc && P.row) {
+    std::vector<D2HSeg> segs;
+    if (col) segs.push_back({(const char*)d_col, (char*)col, (size_t)total * 4});
+    for (int q = 0; q < 3; q++)
+      if (h_e[q]) segs.push_back({(const char*)d_e[q], (char*)h_e[q], (size_t)total * 8});
+    rc = d2h_pageable(ctx, segs);
+  }
+  cleanup();
+  return rc;
 }
 
 int alifmm_time_between_points(alifmm_ctx* ctx, int n, const double* x1, const double* x2, const double* y1,

@@ -161,6 +161,17 @@ struct alifmm_ctx {
   } tfm;
   int tfm_chunk = af::kTfmChunk;  // receivers per register chunk of the TFM kernel (4, 8, 16, 32)
   double t_tfm_upload = 0, t_tfm_kernel = 0;  // last alifmm_tfm (ms)
+  // alifmm_ray_sens: grow-only device buffers (a chunk of host points, the per-ray arrays of a
+  // request, the three maps), freed with the context; the row arrays live for one call
+  struct SensBufs {
+    double* xy = nullptr;
+    long long *off = nullptr, *cnt = nullptr, *row = nullptr;
+    int *len = nullptr, *flags = nullptr, *status = nullptr;
+    double *w = nullptr, *maps = nullptr;
+    size_t xy_n = 0, off_n = 0, cnt_n = 0, row_n = 0, len_n = 0, flags_n = 0, status_n = 0, w_n = 0, maps_n = 0;
+  } sens;
+  double t_sens_upload = 0, t_sens_kernel = 0;  // last alifmm_ray_sens (ms)
+  int64_t sens_entries = 0;                     // its entries (row_ptr[nrays])
 };
 
 // the band width in force for the resident model on the subgrid-sg grid, and the far band's (0: off)

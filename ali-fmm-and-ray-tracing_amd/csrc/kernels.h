@@ -150,6 +150,31 @@ struct LocalOpsParams {
   int quant;
 };
 
+// alifmm_ray_sens (ray_sens.hip): rays ray0 .. ray0 + nrays - 1 of a request, whose packed points
+// (x, z interleaved) lie in xy from the request's point pt0 on.  The per-ray arrays cover the whole
+// request and are indexed by the ray's number in it.
+struct SensParams {
+  DevModel M;
+  int sg;
+  double dnx;
+  int ray0, nrays;
+  const double* xy;
+  long long pt0;
+  const long long* off;  // first point of each ray (prefix sum of the lengths)
+  const int* len;        // points per ray
+  const int* flags;      // nullable: rays with bit 1 or 2 are skipped
+  const double* w;       // nullable: ray weights of the maps (1)
+  long long* cnt;        // entries per ray: written by the count kernel (0 for a skipped or an invalid
+                         // ray), read by the fill kernel
+  int* status;           // count kernel: 1 for an invalid ray, else 0
+  const long long* row;  // fill, rows: first entry of each ray
+  int* col;              // fill, rows (each nullable)
+  double* elen;
+  double* etime;
+  double* edth;
+  double* maps;          // fill, nullable: [3][nz0][nx0], zeroed by the host
+};
+
 }  // namespace af
 
 extern "C" {
@@ -176,4 +201,7 @@ hipError_t af_launch_tbp(const af::DevModel* M, int n, const double* x1, const d
                          const double* y2, double dnx, int sg, double* out, hipStream_t stream);
 // TFM delay-and-sum (tfm.hip); chunk = receivers per register chunk: 4, 8, 16 or 32
 hipError_t af_launch_tfm(const af::TfmParams* P, int chunk, hipStream_t stream);
+// travel-time sensitivities along rays (ray_sens.hip): the count pass, then the fill pass
+hipError_t af_launch_sens_count(const af::SensParams* P, hipStream_t stream);
+hipError_t af_launch_sens_fill(const af::SensParams* P, hipStream_t stream);
 }

@@ -206,6 +206,68 @@ int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, in
                const float* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
                int niz, int nix, int step, double* image);
 
+/* Travel-time sensitivities along rays: for every ray, the derivative of its time of flight in
+ * every coarse cell it crosses (Fermat: to first order the path is fixed) — the rows of the
+ * travel-time tomography Jacobian, and / or their weighted sums over the rays as three maps on the
+ * coarse grid (with residuals as weights: the misfit gradient J^T r, beside a coverage map).  The
+ * reference carries the pieces (slown_d_slown_stif :3468, travel_times :3026) but never uses them.
+ *   subgrid            the points' subgrid
+ *   ray_len[nrays]     points per ray
+ *   flags (nullable)   the flags of alifmm_find_rays
+ *   ray_xy (nullable)  packed points on the fine grid of `subgrid`, in the layout of
+ *                      alifmm_find_rays (ray k's x at ray_xy[2*off[k] + 2*i], z at +1, off[k] = sum
+ *                      of ray_len[0..k-1]); uploaded in chunks into grow-only buffers of the context.
+ *                      NULL: the points kept on the device by the last alifmm_find_rays(..., NULL,
+ *                      ALIFMM_KEEP_RAYS), read in place; they stay kept for alifmm_take_rays.  Only
+ *                      the device-resident keep (one subgrid in that call, which the caller passes
+ *                      here) is supported: ALIFMM_E_ARG for points staged on the host (several
+ *                      subgrids in one call), and unless ray_len adds up to the kept count
+ *   ray_w (nullable)   float64 [nrays] weights of the maps (1)
+ *   maps (nullable)    float64 [3][nnz][nnx]: sum_k w_k len, sum_k w_k time, sum_k w_k dth per cell
+ *   row_ptr (nullable) int64 [nrays + 1]: the entries of ray k are row_ptr[k] .. row_ptr[k+1] - 1
+ *   cap, col (int32), len, time, dth (float64), each [cap], each nullable: the entries (CSR)
+ *   ray_status (nullable) int32 [nrays]: 1 for an invalid ray (below), else 0
+ * A ray is its points; segment i joins points i and i + 1 and is walked exactly as
+ * time_between_points() (:2835-2989) walks it, piece by piece (a piece ends where the segment
+ * crosses a half-integer cell edge).  Every piece yields one entry, in walk order, segments in
+ * order; entries are neither merged nor sorted (a cell may occur more than once in a row):
+ *   col   y_pos * nnx + x_pos, the piece's coarse cell (the rounded midpoint, a negative index
+ *         wrapped once as numba wraps it)
+ *   len   piece_dist [m]
+ *   time  len * s [s], s = 1 / group_vel_cell(cell, eff), eff = pymod(veln - angle, 180): the very
+ *         summand of time_between_points(); the ordered sum of a ray's time entries is its time
+ *   dth   len * ds [s per degree of the cell's veln]
+ * ds: with h = 2^-10 degree and s(e) = 1 / group_vel_cell(cell, e),
+ *   ds = (s(pymod(eff + h, 180)) - s(pymod(eff - h, 180))) * 512,
+ * except ds = 0 for a Christoffel cell (velpn == 0 with a stiffness row) inside the reference's
+ * on-axis snap (eff % 90 < 0.01 or > 89.99), as slown_d_slown_stif returns there.  One rule for
+ * every material kind: on a table material it is the table's slope, except within h of a knot.  h
+ * is part of the contract: truncation (~ h^2 / 6 s''') and rounding (~ 2^-53 s / h) both come to
+ * ~1e-9 of a typical derivative there.  dth inherits the snap's tiny discontinuity next to the axes
+ * (within h of the snap one of the two slownesses is the snapped one).  The derivative in the
+ * velocity scale needs no output of its own: d t / d vel_map[c] = - time_c / vel_map[c].
+ * A ray contributes nothing (no entries, nothing in the maps) when flags[k] has bit 1 or bit 2 set
+ * (the rays alifmm_find_rays cut short and never times), when ray_len[k] < 2, or when it is
+ * invalid, ray_status[k] = 1: a coordinate is not finite, a piece's cell lies outside the grid after
+ * the wrap, or a segment is unfinished after B = floor|x2 - x1| + floor|y2 - y1| + 4 pieces
+ * (coordinates after the division by subgrid).  No finite walk needs more than B pieces, and the
+ * bound is what ends the call on any input: a horizontal segment at z = k + 0.5, k odd, never sets
+ * fin_y in time_between_points() (a vertical one at x = k + 0.5 never fin_x) and would walk off the
+ * grid without end.
+ * The rows are bit-reproducible, and a ray's rows depend neither on its place in the request nor
+ * on its neighbours.  The maps are accumulated with float64 atomic adds, in no fixed order: they are
+ * reproducible to rounding only, not bit for bit (a ray of weight 0 adds nothing).
+ * Sizing: row_ptr alone (no row array) runs the count pass only; with a row array cap must be >=
+ * row_ptr[nrays], else ALIFMM_E_ARG, row_ptr still holding the sizes.  All offsets are 64-bit.
+ * ALIFMM_E_ARG with a message, the context staying usable, also when: the context has no model;
+ * subgrid < 1; nrays < 0; ray_len is NULL; nothing is requested (maps, row_ptr and ray_status NULL);
+ * a row array without row_ptr.  One GPU: maps of rays traced on several GPUs add on the host.
+ * alifmm_get_option: "sens_upload_ms" (host -> device copies), "sens_kernel_ms" (count and fill
+ * kernels) and "sens_entries" (row_ptr[nrays]) of the last call. */
+int alifmm_ray_sens(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_len, const int32_t* flags,
+                    const double* ray_xy, const double* ray_w, double* maps, int64_t* row_ptr, int64_t cap,
+                    int32_t* col, double* len, double* time, double* dth, int32_t* ray_status);
+
 /* n straight-segment times on the resident model (time_between_points() :2835-2989; the
  * coordinates are fine-grid indices of `subgrid`).  ray_time() (:2992-3022) = ordered sum. */
 int alifmm_time_between_points(alifmm_ctx* ctx, int n, const double* x1, const double* x2, const double* y1,
