@@ -813,6 +813,31 @@ class ALI_FMM:
         ray_len = self.ray_len[i, j]
         return self.ray_paths_x[i, j, 0:ray_len], self.ray_paths_y[i, j, 0:ray_len]
 
+    def _stored_rays(self, pairs):
+        """The rays `pairs` (None: every traced ray, row-major) of the last find_all_TTF_rays* call
+        as a sensitivity request, and the context with the model they were traced on resident:
+        (ii, jj, points per ray, packed points, context)."""
+        if getattr(self, "rays", None) is None:
+            raise ValueError("no rays: call find_all_TTF_rays* with save_rays=True first")
+        store = self.rays
+        if pairs is None:
+            ii, jj = np.nonzero(store.ray_len)
+        else:
+            pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+            ii, jj = pairs[:, 0], pairs[:, 1]
+        lens = store.ray_len[ii, jj].astype(np.int64)
+        offs = store.ray_off[ii, jj]
+        total = int(lens.sum())
+        # row of every point in the store: ray k's points are offs[k] .. offs[k] + lens[k] - 1
+        idx = np.repeat(offs - (np.cumsum(lens) - lens), lens) + np.arange(total)
+        pts = store.points[idx]
+        veln, velpn, vel_map, stif_den = self._ray_model
+        mtab = (veln, velpn, vel_map, stif_den, self.velocity_dat, self.phase_vel)
+        ctx = self._ctx(0)
+        _load_model(ctx, *mtab, self.dnx, self.dnz, self.gox, self.goz,
+                    key=_model_key(*mtab, self.dnx, self.dnz, self.gox, self.goz))
+        return ii, jj, lens, pts, ctx
+
     def ray_sensitivity(self, weights=None, pairs=None, rows=False):
         """Travel-time sensitivities along the rays of the last find_all_TTF_rays* call (not in the
         reference, which stops at slown_d_slown_stif :3468 and travel_times :3026): what a
@@ -829,35 +854,50 @@ class ALI_FMM:
         The store holds coordinates on the model grid, so they are walked with subgrid 1:
         time_between_points() divides by the subgrid first, so the bits are those of the fine
         coordinates.  One GPU; maps of several GPUs add on the host."""
-        if getattr(self, "rays", None) is None:
-            raise ValueError("no rays: call find_all_TTF_rays* with save_rays=True first")
-        store = self.rays
-        if pairs is None:
-            ii, jj = np.nonzero(store.ray_len)
-        else:
-            pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-            ii, jj = pairs[:, 0], pairs[:, 1]
-        lens = store.ray_len[ii, jj].astype(np.int64)
-        offs = store.ray_off[ii, jj]
-        total = int(lens.sum())
-        # row of every point in the store: ray k's points are offs[k] .. offs[k] + lens[k] - 1
-        idx = np.repeat(offs - (np.cumsum(lens) - lens), lens) + np.arange(total)
-        pts = store.points[idx]
+        ii, jj, lens, pts, ctx = self._stored_rays(pairs)
         w = None
         if weights is not None:
             weights = np.asarray(weights, dtype=np.float64)
-            if weights.shape != store.ray_len.shape:
+            if weights.shape != self.rays.ray_len.shape:
                 raise ValueError("weights must have shape (n, n)")
             w = weights[ii, jj]
-        veln, velpn, vel_map, stif_den = self._ray_model
-        mtab = (veln, velpn, vel_map, stif_den, self.velocity_dat, self.phase_vel)
-        ctx = self._ctx(0)
-        _load_model(ctx, *mtab, self.dnx, self.dnz, self.gox, self.goz,
-                    key=_model_key(*mtab, self.dnx, self.dnz, self.gox, self.goz))
         maps, csr, _ = ctx.ray_sens(lens, pts, subgrid=1, weights=w, maps=True, rows=rows)
         if not rows:
             return maps
         return maps, csr, np.stack([ii, jj], axis=1)
+
+    def tomography_step(self, residuals, param="veln", damp=1e-3, smooth=0.0, max_iter=50, tol=1e-6, pairs=None,
+                        mask=None):
+        """One damped, smoothed Gauss-Newton step of a time-of-flight inversion on the rays of the
+        last find_all_TTF_rays* call, solved on the GPU (alifmm_sens_op_build, alifmm_sens_op_solve;
+        not in the reference): the delta that minimises
+        |J delta - residuals|² + damp² |delta|² + smooth² |D delta|², J the Jacobian of the rays'
+        times in `param` on the model they were traced on, D the first differences between
+        neighbouring cells, by CGLS from 0.
+
+        residuals: (n, n) array, residuals[i, j] = measured - computed time of ray (i, j).
+        param: "veln" (orientation [degree]), "vel_map" (velocity scale: d t / d vel_map[c] =
+        -time_c / vel_map[c]) or "slowness" (a slowness change [s / m]: the path lengths).
+        pairs: the rays to take, a sequence of (i, j); None: every traced ray, row-major.
+        mask: (nnz, nnx), 0 freezes a cell (its delta is exactly 0, and it takes no part in the
+        smoothing); None: every cell is free.
+        Returns (delta (nnz, nnx), info): info as Context.sens_op_solve's.  The operator stays
+        resident in the context (Context.sens_op_apply) until the next step or model.  One GPU."""
+        quantity = {"slowness": 0, "vel_map": 1, "veln": 2}.get(param)
+        if quantity is None:
+            raise ValueError("param must be 'veln', 'vel_map' or 'slowness'")
+        ii, jj, lens, pts, ctx = self._stored_rays(pairs)
+        residuals = np.asarray(residuals, dtype=np.float64)
+        if residuals.shape != self.rays.ray_len.shape:
+            raise ValueError("residuals must have shape (n, n)")
+        cs = None if mask is None else (np.asarray(mask) != 0).astype(np.float64)
+        if param == "vel_map":
+            vel_map = np.asarray(self._ray_model[2], dtype=np.float64)
+            cs = -(np.ones(vel_map.shape) if cs is None else cs) / vel_map
+        if cs is not None and cs.shape != tuple(ctx.shape):
+            raise ValueError("mask must have the model's shape")
+        ctx.sens_op_build(lens, pts, subgrid=1, quantity=quantity, col_scale=cs)
+        return ctx.sens_op_solve(residuals[ii, jj], damp=damp, smooth=smooth, max_iter=max_iter, tol=tol)
 
     def save_ray_store(self, path):
         """Write the last call's rays in the compact layout (raystore.RayStore.save: ray_len,

@@ -82,6 +82,10 @@ def _load():
             "alifmm_put_field": (_i, [_p, _i, _i, _p]),
             "alifmm_tfm": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
             "alifmm_ray_sens": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p]),
+            "alifmm_sens_op_build": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
+            "alifmm_sens_op_apply": (_i, [_p, _i, _p, _p]),
+            "alifmm_sens_op_solve": (_i, [_p, _p, _d, _d, _i, _d, _p, _p]),
+            "alifmm_sens_op_release": (_i, [_p]),
             "alifmm_time_between_points": (_i, [_p, _i, _p, _p, _p, _p, _i, _p]),
             "alifmm_local_ops": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i,
                                       _p]),
@@ -464,6 +468,64 @@ class Context:
         arrays = (np.empty(cap, dtype=np.int32), np.empty(cap), np.empty(cap), np.empty(cap))
         call(m, row_ptr, cap, arrays)
         return m, (row_ptr,) + arrays, status
+
+    SOLVE_REASONS = ("tol", "max_iter", "breakdown")
+
+    def sens_op_build(self, ray_len, ray_xy=None, subgrid=1, flags=None, quantity=1, col_scale=None):
+        """Build and keep on the device the operator A (nrays x nnz*nnx) of one quantity of the rays'
+        sensitivities (alifmm_sens_op_build): quantity 0 len, 1 time, 2 dth; col_scale (nnz, nnx)
+        scales the columns (0 freezes a cell).  The request is ray_sens's.  Returns (entries,
+        status)."""
+        lens = _ci32(np.atleast_1d(ray_len))
+        n = len(lens)
+        xy = None
+        if ray_xy is not None:
+            xy = _c64(ray_xy).reshape(-1, 2)
+            if len(xy) != int(np.maximum(lens, 0).sum(dtype=np.int64)):
+                raise ValueError("ray_xy holds %d points, ray_len adds up to %d"
+                                 % (len(xy), int(np.maximum(lens, 0).sum(dtype=np.int64))))
+        fl = None if flags is None else _ci32(np.atleast_1d(flags))
+        if fl is not None and len(fl) != n:
+            raise ValueError("flags must have one value per ray")
+        cs = None
+        if col_scale is not None:
+            cs = _c64(col_scale)
+            if cs.size != int(np.prod(self.shape)):
+                raise ValueError("col_scale must have one value per cell of the model")
+        status = np.zeros(n, dtype=np.int32)
+        entries = ctypes.c_int64(0)
+        self._chk(lib().alifmm_sens_op_build(self._h, int(subgrid), n, _ptr(lens), _ptr(fl), _ptr(xy), int(quantity),
+                                             _ptr(cs), ctypes.addressof(entries), _ptr(status)), "sens_op_build")
+        self._op_rays = n
+        return entries.value, status
+
+    def sens_op_apply(self, v, transpose=False):
+        """A v (v one value per cell; returns one per ray), or with transpose Aᵀ v (v one value per
+        ray; returns (nnz, nnx)), by the resident operator.  Bit-reproducible."""
+        nrays, ncell = getattr(self, "_op_rays", 0), int(np.prod(self.shape))
+        v = _c64(v).ravel()
+        if len(v) != (nrays if transpose else ncell):
+            raise ValueError("the vector has %d values, the operator wants %d" % (len(v), nrays if transpose else ncell))
+        out = np.zeros(ncell if transpose else nrays)
+        self._chk(lib().alifmm_sens_op_apply(self._h, int(bool(transpose)), _ptr(v), _ptr(out)), "sens_op_apply")
+        return out.reshape(self.shape) if transpose else out
+
+    def sens_op_solve(self, rhs, damp=0.0, smooth=0.0, max_iter=50, tol=1e-6):
+        """CGLS on min |A x - rhs|² + damp² |x|² + smooth² |D x|² from x = 0 with the resident operator
+        (alifmm_sens_op_solve).  Returns (x (nnz, nnx), info): info = dict(iterations, grad0, grad,
+        rhs_norm, res_norm, reason ("tol", "max_iter" or "breakdown"), entries)."""
+        rhs = _c64(rhs).ravel()
+        if len(rhs) != getattr(self, "_op_rays", 0):
+            raise ValueError("rhs has %d values, the operator has %d rays" % (len(rhs), getattr(self, "_op_rays", 0)))
+        x = np.zeros(self.shape)
+        info = np.zeros(8)
+        self._chk(lib().alifmm_sens_op_solve(self._h, _ptr(rhs), float(damp), float(smooth), int(max_iter), float(tol),
+                                             _ptr(x), _ptr(info)), "sens_op_solve")
+        return x, {"iterations": int(info[0]), "grad0": info[1], "grad": info[2], "rhs_norm": info[3],
+                   "res_norm": info[4], "reason": self.SOLVE_REASONS[int(info[5])], "entries": int(info[6])}
+
+    def sens_op_release(self):
+        self._chk(lib().alifmm_sens_op_release(self._h), "sens_op_release")
 
     def source_stats(self, slot):
         steps = np.zeros(4, dtype=np.int64)

@@ -219,7 +219,15 @@ int alifmm_ctx_create(int device, alifmm_ctx** out) {
   return ALIFMM_OK;
 }
 
+// the resident sensitivity operator (alifmm_sens_op_build): it belongs to the model it was built on
+static void sens_op_free(alifmm_ctx* c) {
+  auto& o = c->op;
+  dfree(o.row_ptr); dfree(o.col_ptr); dfree(o.col); dfree(o.row); dfree(o.cols); dfree(o.val); dfree(o.cval); dfree(o.cs);
+  o = alifmm_ctx::SensOpBufs();
+}
+
 static void free_model(alifmm_ctx* c) {
+  sens_op_free(c);
   dfree(c->d_veln); dfree(c->d_vm); dfree(c->d_velpn); dfree(c->d_sidx); dfree(c->d_stab); dfree(c->d_gtab);
   dfree(c->d_ptab); dfree(c->d_mid); dfree(c->d_mid8); dfree(c->d_mid8b); dfree(c->d_mtab); dfree(c->d_mslo);
   c->d_mid = nullptr;
@@ -270,6 +278,8 @@ int alifmm_ctx_destroy(alifmm_ctx* ctx) {
     dfree(b.maps);
     b = alifmm_ctx::SensBufs();
   }
+  dfree(ctx->solve.cell); dfree(ctx->solve.ray); dfree(ctx->solve.small);
+  ctx->solve = alifmm_ctx::SolveBufs();
   for (int b = 0; b < alifmm_ctx::kPinBufs; b++) {
     if (ctx->pin[b]) (void)hipHostFree(ctx->pin[b]);
     if (ctx->pin_ev[b]) (void)hipEventDestroy(ctx->pin_ev[b]);
@@ -355,6 +365,12 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "sens_upload_ms")) *value = ctx->t_sens_upload;
   else if (!strcmp(name, "sens_kernel_ms")) *value = ctx->t_sens_kernel;
   else if (!strcmp(name, "sens_entries")) *value = (double)ctx->sens_entries;
+  // the resident operator: its build (the whole call, host clock, ms) and entries (0: none resident);
+  // the last alifmm_sens_op_apply or _solve: device time (HIP events, ms), CGLS iterations
+  else if (!strcmp(name, "solve_build_ms")) *value = ctx->t_solve_build;
+  else if (!strcmp(name, "solve_kernel_ms")) *value = ctx->t_solve_kernel;
+  else if (!strcmp(name, "solve_iters")) *value = ctx->solve_iters;
+  else if (!strcmp(name, "sens_op_entries")) *value = ctx->op.have ? (double)ctx->op.A.entries : 0.0;
   else return fail(ctx, ALIFMM_E_ARG, "unknown option: %s", name);
   return ALIFMM_OK;
 }
@@ -1698,46 +1714,91 @@ int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, in
   return ALIFMM_OK;
 }
 
-int alifmm_ray_sens(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_len, const int32_t* flags,
-                    const double* ray_xy, const double* ray_w, double* maps, int64_t* row_ptr, int64_t cap,
-                    int32_t* col, double* len, double* time, double* dth, int32_t* ray_status) {
-  if (!ctx) return ALIFMM_E_ARG;
-  if (!ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "ray_sens: no model");
-  if (subgrid < 1) return fail(ctx, ALIFMM_E_ARG, "ray_sens: subgrid %d", subgrid);
-  if (nrays < 0) return fail(ctx, ALIFMM_E_ARG, "ray_sens: nrays %d", nrays);
-  if (!ray_len) return fail(ctx, ALIFMM_E_ARG, "ray_sens: ray_len is NULL");
-  const bool want_rows = col || len || time || dth;
-  if (!maps && !row_ptr && !want_rows && !ray_status)
-    return fail(ctx, ALIFMM_E_ARG, "ray_sens: nothing requested (maps, row_ptr and ray_status are NULL)");
-  if (want_rows && !row_ptr) return fail(ctx, ALIFMM_E_ARG, "ray_sens: row arrays without row_ptr");
+// The front half of a sensitivity request, shared by alifmm_ray_sens and alifmm_sens_op_build (`what`
+// names the caller in messages): the rays' first points, the chunks of whole rays whose points are
+// on the device together, the per-ray arrays uploaded, the count pass run, and the row offsets and
+// status of every ray on the host.  run_chunk then runs the fill pass chunk by chunk.
+struct SensRequest {
+  struct Chunk {
+    int r0, r1;       // [first ray, end ray)
+    const double* d;  // device pointer (kept points) or null (host points, uploaded into the context's buffer)
+  };
+  const char* what = "";
+  const double* ray_xy = nullptr;
+  std::vector<long long> off, rows;
+  std::vector<int32_t> status;
+  std::vector<Chunk> chunks;
+  af::SensParams P;
+  int resident = -1;  // the host chunk whose points the context's buffer holds
+  long long total = 0;
+};
+
+static int sens_check_args(alifmm_ctx* ctx, const char* what, int subgrid, int nrays, const int32_t* ray_len) {
+  if (!ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "%s: no model", what);
+  if (subgrid < 1) return fail(ctx, ALIFMM_E_ARG, "%s: subgrid %d", what, subgrid);
+  if (nrays < 0) return fail(ctx, ALIFMM_E_ARG, "%s: nrays %d", what, nrays);
+  if (!ray_len) return fail(ctx, ALIFMM_E_ARG, "%s: ray_len is NULL", what);
+  return ALIFMM_OK;
+}
+
+// the chunk's points on the device, then one pass (count or fill) over its rays
+static int sens_run_chunk(alifmm_ctx* ctx, SensRequest& R, int ci, bool fill) {
+  alifmm_ctx::SensBufs& B = ctx->sens;
+  af::SensParams& P = R.P;
+  const SensRequest::Chunk& c = R.chunks[ci];
+  const long long n = R.off[c.r1] - R.off[c.r0];
+  if (c.d) {
+    P.xy = c.d;
+  } else {
+    if (R.resident != ci) {
+      HIPCHK(dgrow(&B.xy, &B.xy_n, (size_t)2 * std::max<long long>(n, 1)));
+      const auto t0 = std::chrono::steady_clock::now();
+      if (n) HIPCHK(hipMemcpy(B.xy, R.ray_xy + 2 * R.off[c.r0], (size_t)n * 16, hipMemcpyHostToDevice));
+      ctx->t_sens_upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      R.resident = ci;
+    }
+    P.xy = B.xy;
+  }
+  P.pt0 = R.off[c.r0];
+  P.ray0 = c.r0;
+  P.nrays = c.r1 - c.r0;
+  HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+  HIPCHK(fill ? af_launch_sens_fill(&P, ctx->stream) : af_launch_sens_count(&P, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+  ctx->t_sens_kernel += ms;
+  return ALIFMM_OK;
+}
+
+static int sens_count_pass(alifmm_ctx* ctx, SensRequest& R, int subgrid, int nrays, const int32_t* ray_len,
+                           const int32_t* flags, const double* ray_xy, const double* ray_w) {
+  const char* what = R.what;
+  R.ray_xy = ray_xy;
   // the rays' first points; a length below 0 counts as no points
-  std::vector<long long> off((size_t)nrays + 1, 0);
+  std::vector<long long>& off = R.off;
+  off.assign((size_t)nrays + 1, 0);
   for (int k = 0; k < nrays; k++) off[k + 1] = off[k] + std::max(ray_len[k], 0);
   const long long npts = off[nrays];
-  // chunks of whole rays whose points are on the device together: [first ray, end ray), device
-  // pointer (kept points) or null (host points, uploaded into the context's buffer)
-  struct Chunk {
-    int r0, r1;
-    const double* d;
-  };
-  std::vector<Chunk> chunks;
+  std::vector<SensRequest::Chunk>& chunks = R.chunks;
   if (!ray_xy) {
     if (!ctx->kept_rays.empty())
-      return fail(ctx, ALIFMM_E_ARG, "ray_sens: the kept rays are staged on the host (several subgrids in one "
-                                     "find_rays call); pass their points as ray_xy");
+      return fail(ctx, ALIFMM_E_ARG, "%s: the kept rays are staged on the host (several subgrids in one "
+                                     "find_rays call); pass their points as ray_xy", what);
     if (npts != ctx->kept_pts)
-      return fail(ctx, ALIFMM_E_ARG, "ray_sens: ray_len adds up to %lld points, %lld are kept", npts,
+      return fail(ctx, ALIFMM_E_ARG, "%s: ray_len adds up to %lld points, %lld are kept", what, npts,
                   (long long)ctx->kept_pts);
     int r = 0;
     for (auto& k : ctx->kept_dev) {
       const long long end = off[r] + k.npts;
       int r1 = r;
       while (r1 < nrays && off[r1 + 1] <= end) r1++;
-      if (off[r1] != end) return fail(ctx, ALIFMM_E_ARG, "ray_sens: ray_len does not match the kept rays");
+      if (off[r1] != end) return fail(ctx, ALIFMM_E_ARG, "%s: ray_len does not match the kept rays", what);
       if (r1 > r) chunks.push_back({r, r1, k.d});
       r = r1;
     }
-    if (r != nrays && off[r] != npts) return fail(ctx, ALIFMM_E_ARG, "ray_sens: ray_len does not match the kept rays");
+    if (r != nrays && off[r] != npts) return fail(ctx, ALIFMM_E_ARG, "%s: ray_len does not match the kept rays", what);
   } else {
     const long long kChunkPts = 1LL << 24;  // 256 MB of points per upload (a longer ray is a chunk of its own)
     for (int r = 0; r < nrays;) {
@@ -1749,7 +1810,7 @@ int alifmm_ray_sens(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_
   }
   HIPCHK(hipSetDevice(ctx->device));
   alifmm_ctx::SensBufs& B = ctx->sens;
-  const size_t nr = (size_t)nrays, ncell = (size_t)ctx->nz0 * ctx->nx0;
+  const size_t nr = (size_t)nrays;
   ctx->t_sens_upload = ctx->t_sens_kernel = 0;
   ctx->sens_entries = 0;
   auto now = [] { return std::chrono::steady_clock::now(); };
@@ -1772,7 +1833,7 @@ int alifmm_ray_sens(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_
     }
     ctx->t_sens_upload += ms_since(t0);
   }
-  af::SensParams P;
+  af::SensParams& P = R.P;
   memset(&P, 0, sizeof P);
   P.M = dev_model(ctx);
   P.sg = subgrid;
@@ -1783,54 +1844,46 @@ int alifmm_ray_sens(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_
   P.w = ray_w ? B.w : nullptr;
   P.cnt = B.cnt;
   P.status = B.status;
-  int resident = -1;  // the host chunk whose points the context's buffer holds
-  // the chunk's points on the device, then one pass (count or fill) over its rays
-  auto run_chunk = [&](int ci, bool fill) -> int {
-    const Chunk& c = chunks[ci];
-    const long long n = off[c.r1] - off[c.r0];
-    if (c.d) {
-      P.xy = c.d;
-    } else {
-      if (resident != ci) {
-        HIPCHK(dgrow(&B.xy, &B.xy_n, (size_t)2 * std::max<long long>(n, 1)));
-        const auto t0 = now();
-        if (n) HIPCHK(hipMemcpy(B.xy, ray_xy + 2 * off[c.r0], (size_t)n * 16, hipMemcpyHostToDevice));
-        ctx->t_sens_upload += ms_since(t0);
-        resident = ci;
-      }
-      P.xy = B.xy;
-    }
-    P.pt0 = off[c.r0];
-    P.ray0 = c.r0;
-    P.nrays = c.r1 - c.r0;
-    HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    HIPCHK(fill ? af_launch_sens_fill(&P, ctx->stream) : af_launch_sens_count(&P, ctx->stream));
-    HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-    ctx->t_sens_kernel += ms;
-    return ALIFMM_OK;
-  };
   int rc = ALIFMM_OK;
   for (int ci = 0; ci < (int)chunks.size(); ci++)
-    if ((rc = run_chunk(ci, false))) return rc;
+    if ((rc = sens_run_chunk(ctx, R, ci, false))) return rc;
   // row offsets (rays outside every chunk have no points: no entries, status 0)
-  std::vector<long long> rows(nr + 1, 0);
-  std::vector<int32_t> status(nr, 0);
+  R.rows.assign(nr + 1, 0);
+  R.status.assign(nr, 0);
   {
     std::vector<long long> cnt(nr, 0);
-    for (const Chunk& c : chunks) {
+    for (const SensRequest::Chunk& c : chunks) {
       HIPCHK(hipMemcpy(cnt.data() + c.r0, B.cnt + c.r0, (size_t)(c.r1 - c.r0) * 8, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemcpy(status.data() + c.r0, B.status + c.r0, (size_t)(c.r1 - c.r0) * 4, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(R.status.data() + c.r0, B.status + c.r0, (size_t)(c.r1 - c.r0) * 4, hipMemcpyDeviceToHost));
     }
-    for (size_t k = 0; k < nr; k++) rows[k + 1] = rows[k] + cnt[k];
+    for (size_t k = 0; k < nr; k++) R.rows[k + 1] = R.rows[k] + cnt[k];
   }
-  const long long total = rows[nr];
-  ctx->sens_entries = total;
+  R.total = R.rows[nr];
+  ctx->sens_entries = R.total;
+  return ALIFMM_OK;
+}
+
+int alifmm_ray_sens(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_len, const int32_t* flags,
+                    const double* ray_xy, const double* ray_w, double* maps, int64_t* row_ptr, int64_t cap,
+                    int32_t* col, double* len, double* time, double* dth, int32_t* ray_status) {
+  if (!ctx) return ALIFMM_E_ARG;
+  if (int rc = sens_check_args(ctx, "ray_sens", subgrid, nrays, ray_len)) return rc;
+  const bool want_rows = col || len || time || dth;
+  if (!maps && !row_ptr && !want_rows && !ray_status)
+    return fail(ctx, ALIFMM_E_ARG, "ray_sens: nothing requested (maps, row_ptr and ray_status are NULL)");
+  if (want_rows && !row_ptr) return fail(ctx, ALIFMM_E_ARG, "ray_sens: row arrays without row_ptr");
+  SensRequest R;
+  R.what = "ray_sens";
+  int rc = sens_count_pass(ctx, R, subgrid, nrays, ray_len, flags, ray_xy, ray_w);
+  if (rc) return rc;
+  alifmm_ctx::SensBufs& B = ctx->sens;
+  af::SensParams& P = R.P;
+  const std::vector<long long>& rows = R.rows;
+  const size_t nr = (size_t)nrays, ncell = (size_t)ctx->nz0 * ctx->nx0;
+  const long long total = R.total;
   if (row_ptr)
     for (size_t k = 0; k <= nr; k++) row_ptr[k] = rows[k];
-  if (ray_status && nrays) memcpy(ray_status, status.data(), nr * 4);
+  if (ray_status && nrays) memcpy(ray_status, R.status.data(), nr * 4);
   if (want_rows && cap < total)
     return fail(ctx, ALIFMM_E_ARG, "ray_sens: cap %lld < %lld entries (row_ptr holds the sizes)", (long long)cap, total);
   if (!maps && !want_rows) return ALIFMM_OK;
@@ -1867,7 +1920,7 @@ int alifmm_ray_sens(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_
     P.edth = d_e[2];
   }
   if (total > 0 && (maps || P.row))
-    for (int ci = 0; ci < (int)chunks.size() && !rc; ci++) rc = run_chunk(ci, true);
+    for (int ci = 0; ci < (int)R.chunks.size() && !rc; ci++) rc = sens_run_chunk(ctx, R, ci, true);
   if (!rc && maps) {
     std::vector<D2HSeg> segs{{(const char*)B.maps, (char*)maps, 3 * ncell * 8}};
     rc = d2h_pageable(ctx, segs);
@@ -1881,6 +1934,223 @@ int alifmm_ray_sens(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_
   }
   cleanup();
   return rc;
+}
+
+int alifmm_sens_op_release(alifmm_ctx* ctx) {
+  if (!ctx) return ALIFMM_E_ARG;
+  (void)hipSetDevice(ctx->device);
+  sens_op_free(ctx);
+  return ALIFMM_OK;
+}
+
+int alifmm_sens_op_build(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_len, const int32_t* flags,
+                         const double* ray_xy, int quantity, const double* col_scale, int64_t* entries,
+                         int32_t* ray_status) {
+  if (!ctx) return ALIFMM_E_ARG;
+  if (int rc = sens_check_args(ctx, "sens_op_build", subgrid, nrays, ray_len)) return rc;
+  if (quantity < 0 || quantity > 2) return fail(ctx, ALIFMM_E_ARG, "sens_op_build: quantity %d (0 len, 1 time, 2 dth)", quantity);
+  const size_t nr = (size_t)nrays, ncell = (size_t)ctx->nz0 * ctx->nx0;
+  if (col_scale)
+    for (size_t c = 0; c < ncell; c++)
+      if (!std::isfinite(col_scale[c])) return fail(ctx, ALIFMM_E_ARG, "sens_op_build: col_scale[%zu] is not finite", c);
+  const auto t0 = std::chrono::steady_clock::now();
+  SensRequest R;
+  R.what = "sens_op_build";
+  int rc = sens_count_pass(ctx, R, subgrid, nrays, ray_len, flags, ray_xy, nullptr);
+  if (rc) return rc;
+  sens_op_free(ctx);  // the request is good: the new operator replaces the resident one
+  const long long total = R.total;
+  if (entries) *entries = total;
+  if (ray_status && nrays) memcpy(ray_status, R.status.data(), nr * 4);
+  if (total >= (1LL << 31))
+    return fail(ctx, ALIFMM_E_CAPACITY, "sens_op_build: %lld entries, an operator holds fewer than 2^31", total);
+  alifmm_ctx::SensOpBufs& O = ctx->op;
+  const size_t ne = (size_t)total;
+  unsigned* scratch = nullptr;  // key | key2 | idx | idx2
+  void* temp = nullptr;
+  int* cursor = nullptr;
+  const size_t temp_bytes = total ? af_solve_sort_temp(total, (long)ncell) : 0;
+  auto drop = [&] {
+    dfree(scratch);
+    dfree(temp);
+    dfree(cursor);
+  };
+  auto bail = [&](hipError_t e) {
+    drop();
+    sens_op_free(ctx);
+    return fail(ctx, ALIFMM_E_HIP, "sens_op_build: %s", hipGetErrorString(e));
+  };
+  hipError_t e = dalloc(&O.row_ptr, nr + 1);
+  if (e == hipSuccess) e = dalloc(&O.col, ne);
+  if (e == hipSuccess) e = dalloc(&O.val, ne);
+  if (e == hipSuccess) e = dalloc(&O.col_ptr, ncell + 1);
+  if (e == hipSuccess) e = dalloc(&O.row, ne);
+  if (e == hipSuccess) e = dalloc(&O.cval, ne);
+  if (e == hipSuccess && col_scale) e = dalloc(&O.cs, ncell);
+  if (e == hipSuccess) e = dalloc(&scratch, 4 * ne);
+  if (e == hipSuccess) e = dalloc((char**)&temp, temp_bytes);
+  if (e == hipSuccess) e = dalloc(&cursor, 3);
+  if (e == hipSuccess) e = hipMemcpy(O.row_ptr, R.rows.data(), (nr + 1) * 8, hipMemcpyHostToDevice);
+  if (e == hipSuccess && col_scale) e = hipMemcpy(O.cs, col_scale, ncell * 8, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return bail(e);
+  // the fill pass writes the CSR in place: the columns and the one quantity
+  af::SensParams& P = R.P;
+  P.row = O.row_ptr;
+  P.col = O.col;
+  (quantity == 0 ? P.elen : quantity == 1 ? P.etime : P.edth) = O.val;
+  if (total > 0)
+    for (int ci = 0; ci < (int)R.chunks.size() && !rc; ci++) rc = sens_run_chunk(ctx, R, ci, true);
+  if (rc) {
+    drop();
+    sens_op_free(ctx);
+    return rc;
+  }
+  af::SensOp& A = O.A;
+  A.nrays = nrays;
+  A.nz = ctx->nz0;
+  A.nx = ctx->nx0;
+  A.ncell = (long)ncell;
+  A.entries = total;
+  A.row_ptr = O.row_ptr;
+  A.col = O.col;
+  A.val = O.val;
+  A.col_ptr = O.col_ptr;
+  A.row = O.row;
+  A.cval = O.cval;
+  A.cs = O.cs;
+  // the transposed copy, then the non-empty columns by length class: counted, then listed
+  e = af_launch_solve_transpose(&A, O.col_ptr, O.row, O.cval, scratch, scratch + ne, scratch + 2 * ne, scratch + 3 * ne,
+                                temp, temp_bytes, ctx->stream);
+  int n3[3] = {0, 0, 0};
+  if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, sizeof n3, ctx->stream);
+  if (e == hipSuccess) e = af_launch_solve_classify(O.col_ptr, (long)ncell, nullptr, cursor, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(n3, cursor, sizeof n3, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = dalloc(&O.cols, (size_t)n3[0] + n3[1] + n3[2]);
+  const int first3[3] = {0, n3[0], n3[0] + n3[1]};
+  if (e == hipSuccess) e = hipMemcpyAsync(cursor, first3, sizeof first3, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = af_launch_solve_classify(O.col_ptr, (long)ncell, O.cols, cursor, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e != hipSuccess) return bail(e);
+  for (int q = 0; q < 3; q++) {
+    A.cols[q] = O.cols + first3[q];
+    A.ncols[q] = n3[q];
+  }
+  drop();
+  O.have = true;
+  ctx->t_solve_build = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return ALIFMM_OK;
+}
+
+int alifmm_sens_op_apply(alifmm_ctx* ctx, int transpose, const double* in, double* out) {
+  if (!ctx) return ALIFMM_E_ARG;
+  if (!ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "sens_op_apply: no model");
+  if (!ctx->op.have) return fail(ctx, ALIFMM_E_ARG, "sens_op_apply: no resident operator (alifmm_sens_op_build)");
+  if (!in || !out) return fail(ctx, ALIFMM_E_ARG, "sens_op_apply: %s is NULL", in ? "out" : "in");
+  const af::SensOp& A = ctx->op.A;
+  const size_t nc = (size_t)A.ncell, nr = (size_t)A.nrays;
+  HIPCHK(hipSetDevice(ctx->device));
+  alifmm_ctx::SolveBufs& S = ctx->solve;
+  HIPCHK(dgrow(&S.cell, &S.cell_n, 5 * nc));
+  HIPCHK(dgrow(&S.ray, &S.ray_n, 2 * nr));
+  double* din = transpose ? S.ray : S.cell;
+  double* dout = transpose ? S.cell : S.ray;
+  const size_t nin = transpose ? nr : nc, nout = transpose ? nc : nr;
+  if (nin) HIPCHK(hipMemcpy(din, in, nin * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+  HIPCHK(transpose ? af_launch_solve_colprod(&A, din, dout, ctx->stream)
+                   : af_launch_solve_rowprod(&A, din, S.cell + nc, dout, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+  ctx->t_solve_kernel = ms;
+  if (nout) HIPCHK(hipMemcpy(out, dout, nout * 8, hipMemcpyDeviceToHost));
+  return ALIFMM_OK;
+}
+
+int alifmm_sens_op_solve(alifmm_ctx* ctx, const double* rhs, double damp, double smooth, int max_iter, double tol,
+                         double* x, double* info8) {
+  if (!ctx) return ALIFMM_E_ARG;
+  if (!ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "sens_op_solve: no model");
+  if (!ctx->op.have) return fail(ctx, ALIFMM_E_ARG, "sens_op_solve: no resident operator (alifmm_sens_op_build)");
+  if (!rhs || !x) return fail(ctx, ALIFMM_E_ARG, "sens_op_solve: %s is NULL", rhs ? "x" : "rhs");
+  if (!(damp >= 0) || !std::isfinite(damp)) return fail(ctx, ALIFMM_E_ARG, "sens_op_solve: damp %g", damp);
+  if (!(smooth >= 0) || !std::isfinite(smooth)) return fail(ctx, ALIFMM_E_ARG, "sens_op_solve: smooth %g", smooth);
+  if (max_iter < 1) return fail(ctx, ALIFMM_E_ARG, "sens_op_solve: max_iter %d", max_iter);
+  if (!(tol >= 0) || !std::isfinite(tol)) return fail(ctx, ALIFMM_E_ARG, "sens_op_solve: tol %g", tol);
+  const af::SensOp& A = ctx->op.A;
+  const size_t nc = (size_t)A.ncell, nr = (size_t)A.nrays;
+  for (size_t k = 0; k < nr; k++)
+    if (!std::isfinite(rhs[k])) return fail(ctx, ALIFMM_E_ARG, "sens_op_solve: rhs[%zu] is not finite", k);
+  HIPCHK(hipSetDevice(ctx->device));
+  alifmm_ctx::SolveBufs& S = ctx->solve;
+  HIPCHK(dgrow(&S.cell, &S.cell_n, 5 * nc));
+  HIPCHK(dgrow(&S.ray, &S.ray_n, 2 * nr));
+  HIPCHK(dgrow(&S.small, &S.small_n, (size_t)af::kSolveMaxParts + af::kSolScalars));
+  af::SolveVecs V;
+  V.x = S.cell;
+  V.p = S.cell + nc;
+  V.s = S.cell + 2 * nc;
+  V.t = S.cell + 3 * nc;
+  V.xs = S.cell + 4 * nc;
+  V.r = S.ray;
+  V.q = S.ray + nr;
+  V.parts = S.small;
+  V.scal = S.small + af::kSolveMaxParts;
+  V.damp2 = damp * damp;
+  V.smooth2 = smooth * smooth;
+  hipStream_t st = ctx->stream;
+  // one scalar of the device's (8 bytes) after the work queued so far
+  auto scalar = [&](int which, double* v) {
+    hipError_t e = hipMemcpyAsync(v, V.scal + which, 8, hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? hipStreamSynchronize(st) : e;
+  };
+  if (nr) HIPCHK(hipMemcpy(V.r, rhs, nr * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipEventRecord(ctx->ev[0], st));
+  HIPCHK(hipMemsetAsync(V.x, 0, 2 * nc * 8, st));  // x = p = 0
+  HIPCHK(hipMemsetAsync(V.scal, 0, af::kSolScalars * 8, st));
+  double rhs2 = 0, gamma0 = 0, gamma = 0, res2 = 0;
+  HIPCHK(af_launch_solve_norm(V.r, (long)nr, &V, st));
+  HIPCHK(scalar(af::kSolNorm, &rhs2));
+  // x = 0: s = Aᵀ rhs, p = s, gamma_0 = |s|²
+  HIPCHK(af_launch_solve_colprod(&A, V.r, V.t, st));
+  HIPCHK(af_launch_solve_start(&A, &V, st));
+  HIPCHK(scalar(af::kSolReport, &gamma0));
+  gamma = gamma0;
+  int iters = 0, reason = 1;
+  if (gamma0 == 0.0) reason = 2;
+  else
+    for (int it = 1; it <= max_iter; it++) {
+      HIPCHK(af_launch_solve_iter(&A, &V, st));
+      double rep = 0;
+      HIPCHK(scalar(af::kSolReport, &rep));  // the one read of an iteration: the new gamma, -1: |q|² was 0
+      if (rep < 0) {
+        reason = 2;
+        break;
+      }
+      gamma = rep;
+      iters = it;
+      if (gamma <= tol * tol * gamma0) {
+        reason = 0;
+        break;
+      }
+    }
+  HIPCHK(af_launch_solve_norm(V.r, (long)nr, &V, st));
+  HIPCHK(scalar(af::kSolNorm, &res2));
+  HIPCHK(hipEventRecord(ctx->ev[1], st));
+  HIPCHK(hipStreamSynchronize(st));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+  ctx->t_solve_kernel = ms;
+  ctx->solve_iters = iters;
+  if (nc) HIPCHK(hipMemcpy(x, V.x, nc * 8, hipMemcpyDeviceToHost));
+  if (info8) {
+    const double info[8] = {(double)iters, sqrt(gamma0), sqrt(gamma), sqrt(rhs2), sqrt(res2), (double)reason,
+                            (double)A.entries, 0.0};
+    memcpy(info8, info, sizeof info);
+  }
+  return ALIFMM_OK;
 }
 
 int alifmm_time_between_points(alifmm_ctx* ctx, int n, const double* x1, const double* x2, const double* y1,

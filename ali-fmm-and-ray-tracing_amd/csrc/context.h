@@ -172,6 +172,22 @@ struct alifmm_ctx {
   } sens;
   double t_sens_upload = 0, t_sens_kernel = 0;  // last alifmm_ray_sens (ms)
   int64_t sens_entries = 0;                     // its entries (row_ptr[nrays])
+  // alifmm_sens_op_*: the resident operator (CSR, CSC, column scale, column lists; A points into
+  // these), freed by alifmm_sens_op_release, alifmm_set_model and with the context; and the grow-only
+  // vectors of apply and solve, freed with the context
+  struct SensOpBufs {
+    bool have = false;
+    af::SensOp A = {};
+    long long *row_ptr = nullptr, *col_ptr = nullptr;
+    int *col = nullptr, *row = nullptr, *cols = nullptr;
+    double *val = nullptr, *cval = nullptr, *cs = nullptr;
+  } op;
+  struct SolveBufs {
+    double *cell = nullptr, *ray = nullptr, *small = nullptr;  // 5 x ncell, 2 x nrays, partial sums + scalars
+    size_t cell_n = 0, ray_n = 0, small_n = 0;
+  } solve;
+  double t_solve_build = 0, t_solve_kernel = 0;  // last sens_op_build (whole call) / apply or solve (device), ms
+  int solve_iters = 0;                           // last alifmm_sens_op_solve
 };
 
 // the band width in force for the resident model on the subgrid-sg grid, and the far band's (0: off)

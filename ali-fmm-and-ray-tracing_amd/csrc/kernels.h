@@ -2,6 +2,7 @@
 #pragma once
 #include "device_common.h"
 #include "fmm_shared.h"
+#include "solve_ops.h"  // the sums' geometry (kSolveMaxParts) of the resident sensitivity operator (sens_solve.hip)
 #include "tfm_term.h"  // af::TfmParams: the parameter block of the TFM kernel (tfm.hip) and of its host model
 
 namespace af {
@@ -175,6 +176,35 @@ struct SensParams {
   double* maps;          // fill, nullable: [3][nz0][nx0], zeroed by the host
 };
 
+// alifmm_sens_op_* (sens_solve.hip): one quantity of the request's Jacobian, resident on the device.
+// A[k][c] = cs[c] * sum of val[e] over the entries e of row k with col[e] == c; rows unmerged.
+struct SensOp {
+  int nrays;
+  int nz, nx;
+  long ncell;
+  long long entries;         // < 2^31
+  const long long* row_ptr;  // CSR [nrays + 1]: the fill pass's order (ray, then walk order)
+  const int* col;
+  const double* val;
+  const long long* col_ptr;  // CSC [ncell + 1]: a column's entries in ascending entry index
+  const int* row;
+  const double* cval;
+  const double* cs;          // [ncell] or null (1)
+  const int* cols[3];        // the non-empty columns by length class (solve_ops.h: thread, wave, workgroup)
+  int ncols[3];
+};
+
+// device vectors and scalars of alifmm_sens_op_solve
+enum { kSolGamma = 0, kSolAlpha, kSolBeta, kSolReport, kSolBreak, kSolNorm, kSolScalars = 8 };
+struct SolveVecs {
+  double *x, *p, *s, *t, *xs;  // [ncell]; t = Aᵀ r, xs = cs p (the row product's scratch)
+  double *r, *q;          // [nrays]
+  double* parts;          // [kSolveMaxParts] partial sums
+  double* scal;           // [kSolScalars]: gamma, alpha, beta, the iteration's report (the new gamma, or
+                          // -1 when |q|² was 0), the breakdown flag, the last af_launch_solve_norm
+  double damp2, smooth2;
+};
+
 }  // namespace af
 
 extern "C" {
@@ -204,4 +234,18 @@ hipError_t af_launch_tfm(const af::TfmParams* P, int chunk, hipStream_t stream);
 // travel-time sensitivities along rays (ray_sens.hip): the count pass, then the fill pass
 hipError_t af_launch_sens_count(const af::SensParams* P, hipStream_t stream);
 hipError_t af_launch_sens_fill(const af::SensParams* P, hipStream_t stream);
+// the resident sensitivity operator (sens_solve.hip).  Transpose: the CSC copy of a CSR (stable radix
+// sort by column), key / key2 / idx / idx2 [entries] and temp (af_solve_sort_temp bytes) being scratch;
+// classify: the non-empty columns by length class, counted (cols null) or listed from the cursors in
+// cursor3 on; the products; CGLS: the start from t = Aᵀ rhs, one iteration, |v|² into scal[kSolNorm]
+size_t af_solve_sort_temp(long long entries, long ncell);
+hipError_t af_launch_solve_transpose(const af::SensOp* A, long long* col_ptr, int* row, double* cval, unsigned* key,
+                                     unsigned* key2, unsigned* idx, unsigned* idx2, void* temp, size_t temp_bytes,
+                                     hipStream_t stream);
+hipError_t af_launch_solve_classify(const long long* col_ptr, long ncell, int* cols, int* cursor3, hipStream_t stream);
+hipError_t af_launch_solve_rowprod(const af::SensOp* A, const double* x, double* xs, double* out, hipStream_t stream);
+hipError_t af_launch_solve_colprod(const af::SensOp* A, const double* y, double* out, hipStream_t stream);
+hipError_t af_launch_solve_start(const af::SensOp* A, const af::SolveVecs* V, hipStream_t stream);
+hipError_t af_launch_solve_iter(const af::SensOp* A, const af::SolveVecs* V, hipStream_t stream);
+hipError_t af_launch_solve_norm(const double* v, long n, const af::SolveVecs* V, hipStream_t stream);
 }

@@ -268,6 +268,77 @@ int alifmm_ray_sens(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_
                     const double* ray_xy, const double* ray_w, double* maps, int64_t* row_ptr, int64_t cap,
                     int32_t* col, double* len, double* time, double* dth, int32_t* ray_status);
 
+/* The inversion step on the device: one quantity of the rays' Jacobian kept in the context as an
+ * operator A (nrays x ncell, ncell = nnz * nnx), products with it in both directions, and the
+ * damped, smoothed least-squares step min |A x - rhs|^2 + damp^2 |x|^2 + smooth^2 |D x|^2 by CGLS.
+ * One coarse-grid map comes back instead of the rows.
+ *
+ * alifmm_sens_op_build
+ *   subgrid, nrays, ray_len, flags, ray_xy   the request, exactly as in alifmm_ray_sens (ray_xy NULL:
+ *                      the points kept by the last alifmm_find_rays(..., NULL, ALIFMM_KEEP_RAYS))
+ *   quantity           0 len, 1 time, 2 dth: which value of an entry the operator holds
+ *   col_scale (nullable) float64 [ncell] cs (1): cs[c] == 0 freezes cell c; cs = -1 / vel_map with
+ *                      quantity 1 gives the Jacobian in the velocity scale
+ *   entries (nullable) the operator's entries = "sens_entries" of alifmm_ray_sens for the request
+ *   ray_status (nullable) int32 [nrays], as alifmm_ray_sens
+ * A[k][c] = cs[c] * (the sum of val[e] over the entries e of ray k with col[e] == c), the entries
+ * being those of alifmm_ray_sens for the same request: the same walk, the same len / time / dth
+ * arithmetic, the same kernels.  A skipped ray (flags bit 1 or 2, fewer than 2 points) and an invalid
+ * one (ray_status 1) are empty rows.  Rows stay unmerged: a cell may occur several times in a row.
+ * The context keeps the rows (CSR: row_ptr, col, val) and a transposed copy (CSC: col_ptr, row,
+ * val) in which every column holds its entries in ascending entry index, that is by ray, then in
+ * walk order (a stable sort by column): the order is a function of the request alone.  About 24
+ * bytes per entry; fewer than 2^31 entries, else ALIFMM_E_CAPACITY.  A build replaces the resident
+ * operator (a build refused with ALIFMM_E_ARG leaves it in place).  The operator is freed by alifmm_sens_op_release, with the context, and by
+ * alifmm_set_model: it belongs to the model it was built on, and after a new model apply and solve
+ * return ALIFMM_E_ARG until the next build.
+ *
+ * alifmm_sens_op_apply    out[nrays] = A in[ncell], or with transpose != 0 out[ncell] = A^T in[nrays]
+ * (host vectors).  Term by term, in float64, no contraction:
+ *   (A x)[k]   = sum over the entries e of row k, of val[e] * (cs[col[e]] * x[col[e]]); an empty row: 0
+ *   (A^T y)[c] = cs[c] * (sum over the entries e of column c, of val[e] * y[row[e]]); an empty column: 0
+ * Every sum has an order fixed by the operator: 256 lanes take a row's entries round robin, each adds
+ * its own in order from 0, the 64 lanes of a wavefront pair up over the lane distances 32, 16, ..., 1,
+ * the four wavefronts as (0 + 1) + (2 + 3); a column of up to 4 entries is added in order by one lane,
+ * of up to 256 by the 64 lanes of one wavefront, a longer one as a row.  There are no float atomics:
+ * two calls, two builds of the same request and two contexts return the same bits, and a ray's
+ * element of A x depends on that ray alone.
+ *
+ * alifmm_sens_op_solve    CGLS from x = 0; D is the first difference over every 4-neighbour pair of
+ * coarse cells that both have cs != 0, so (D^T D p)[c] = sum over those neighbours c' of
+ * (p[c] - p[c']) (upper, left, right, lower, in that order; 0 in a frozen cell).  With
+ * R(v) = damp^2 v + smooth^2 D^T D v:
+ *   r = rhs; s = A^T r; p = s; gamma_0 = gamma = |s|^2; gamma_0 == 0: stop (breakdown)
+ *   iteration it = 1, 2, ...:
+ *     q = A p; qq = |q|^2 + p . R(p); qq == 0: stop (breakdown; the iteration does not count)
+ *     alpha = gamma / qq; x += alpha p; r -= alpha q
+ *     s = A^T r - R(x); gamma' = |s|^2; beta = gamma' / gamma; p = s + beta p; gamma = gamma'
+ *     gamma <= tol^2 gamma_0: stop (tol); it == max_iter: stop (max_iter)
+ * No augmented residual is kept.  All vectors and alpha, beta, gamma stay on the device; the host
+ * reads 8 bytes per iteration for the stop rule.  Every dot product is a two-stage sum in a fixed
+ * order (its partial sums depend on the vector's length alone), so x and info8 are bit-reproducible.
+ * A frozen cell of x is exactly 0.
+ *   rhs   float64 [nrays]; x float64 [ncell]
+ *   info8 (nullable) iterations, sqrt(gamma_0), sqrt(gamma) at the end, |rhs|, the recurred |r| at the
+ *         end, the stop's reason (0 tol, 1 max_iter, 2 breakdown), the operator's entries, 0
+ *
+ * ALIFMM_E_ARG with a message, the context staying usable, when: the context has no model; build:
+ * subgrid < 1, nrays < 0, ray_len NULL, the kept-points errors of alifmm_ray_sens, quantity outside
+ * 0..2, a col_scale that is not finite; apply and solve: no resident operator (never built, released,
+ * or dropped by alifmm_set_model), in, out, rhs or x NULL, an rhs that is not finite, damp or smooth
+ * negative or not finite, max_iter < 1, tol negative or not finite.  A failed device allocation
+ * returns ALIFMM_E_HIP with the operator released.  One GPU.
+ * alifmm_get_option: "solve_build_ms" (the last build, the whole call), "solve_kernel_ms" (device time
+ * of the last apply or solve), "solve_iters" (the last solve) and "sens_op_entries" (the resident
+ * operator's entries, 0 without one). */
+int alifmm_sens_op_build(alifmm_ctx* ctx, int subgrid, int nrays, const int32_t* ray_len, const int32_t* flags,
+                         const double* ray_xy, int quantity, const double* col_scale, int64_t* entries,
+                         int32_t* ray_status);
+int alifmm_sens_op_apply(alifmm_ctx* ctx, int transpose, const double* in, double* out);
+int alifmm_sens_op_solve(alifmm_ctx* ctx, const double* rhs, double damp, double smooth, int max_iter, double tol,
+                         double* x, double* info8);
+int alifmm_sens_op_release(alifmm_ctx* ctx);
+
 /* n straight-segment times on the resident model (time_between_points() :2835-2989; the
  * coordinates are fine-grid indices of `subgrid`).  ray_time() (:2992-3022) = ordered sum. */
 int alifmm_time_between_points(alifmm_ctx* ctx, int n, const double* x1, const double* x2, const double* y1,
