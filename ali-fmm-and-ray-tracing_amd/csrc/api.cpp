@@ -45,7 +45,7 @@ static void release_kept_rays(alifmm_ctx* c) {
   c->kept_pts = 0;
 }
 static void free_arena(Arena& a) {
-  dfree(a.S); dfree(a.lists); dfree(a.dlists); dfree(a.Ts); dfree(a.Ss); dfree(a.srcs); dfree(a.ho); dfree(a.jobs);
+  dfree(a.S); dfree(a.lists); dfree(a.dlists); dfree(a.Ts); dfree(a.Ss); dfree(a.srcs); dfree(a.ho); dfree(a.sig); dfree(a.jobs);
   dfree(a.rimc); dfree(a.rimt); dfree(a.kx); dfree(a.Tb); dfree(a.Sb);
   dfree(a.dscx); dfree(a.dscz);
   a = Arena();
@@ -266,8 +266,12 @@ int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   free_arena(ctx->arena);
   dfree(ctx->ho_all);
   dfree(ctx->jobs_all);
+  dfree(ctx->sig_all);
+  dfree(ctx->reused_all);
   ctx->ho_all = nullptr;
   ctx->jobs_all = nullptr;
+  ctx->sig_all = nullptr;
+  ctx->reused_all = nullptr;
   ctx->ho_last = nullptr;
   free_ray_bufs(ctx);
   dfree(ctx->tfm.fmc); dfree(ctx->tfm.w); dfree(ctx->tfm.tab); dfree(ctx->tfm.img);
@@ -313,6 +317,7 @@ int alifmm_set_option(alifmm_ctx* ctx, const char* name, double value) {
   else if (!strcmp(name, "coop")) ctx->coop = value != 0;
   else if (!strcmp(name, "exact_r") && value >= 0 && value <= 48) ctx->exact_r = (int)value;
   else if (!strcmp(name, "exact_lds")) ctx->exact_lds = value != 0;
+  else if (!strcmp(name, "init_reuse")) ctx->init_reuse = value != 0;
   else if (!strcmp(name, "stream_out")) ctx->stream_out = value != 0;
   else if (!strcmp(name, "members") && value >= 0 && value <= af::kMaxK && value == (int)value)
     ctx->members = (int)value;
@@ -334,10 +339,13 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "batch")) *value = ctx->batch;
   else if (!strcmp(name, "exact_r")) *value = ctx->exact_r;
   else if (!strcmp(name, "exact_lds")) *value = ctx->exact_lds;
+  else if (!strcmp(name, "init_reuse")) *value = ctx->init_reuse;
+  else if (!strcmp(name, "init_reused")) *value = ctx->init_reused;  // last travel call: walks skipped
   else if (!strcmp(name, "stream_out")) *value = ctx->stream_out;
   else if (!strcmp(name, "stream_tail_ms")) *value = ctx->t_stream_tail;      // last travel with a host destination
   else if (!strcmp(name, "stream_fallback")) *value = (double)ctx->stream_fallback;
   else if (!strcmp(name, "exact_redo")) *value = (double)ctx->exact_redo;
+  else if (!strcmp(name, "fill_wait_ms")) *value = ctx->t_fill_wait;  // last travel: fill exposed after the source init
   else if (!strcmp(name, "prof")) *value = ctx->prof;
   else if (!strcmp(name, "coop")) *value = ctx->coop;
   else if (!strcmp(name, "members")) *value = ctx->members;
@@ -530,6 +538,19 @@ int alifmm_set_model(alifmm_ctx* ctx, int nnz, int nnx, const double* veln, cons
       ctx->nmat = (int)recs.size();
     }
   }
+  // the small tables the source-init walk reads: another epoch when any byte of them changed
+  {
+    const size_t nt = (size_t)361 * ncol;
+    if (ctx->tab_epoch == 0 || ctx->h_ncol != ncol || ctx->h_stab.size() != stab.size() ||
+        memcmp(ctx->h_gtab.data(), group_tab, nt * 8) || memcmp(ctx->h_ptab.data(), phase_tab, nt * 8) ||
+        (!stab.empty() && memcmp(ctx->h_stab.data(), stab.data(), stab.size() * 8))) {
+      ctx->h_gtab.assign(group_tab, group_tab + nt);
+      ctx->h_ptab.assign(phase_tab, phase_tab + nt);
+      ctx->h_stab = stab;
+      ctx->h_ncol = ncol;
+      ctx->tab_epoch++;
+    }
+  }
   ctx->nstab = (int)stab.size() / 5;
   ctx->nz0 = nnz;
   ctx->nx0 = nnx;
@@ -621,6 +642,8 @@ static int ensure_arena(alifmm_ctx* ctx, int nsrc, long cells, long scells, long
   }
   HIPCHK(dalloc(&a.srcs, nsrc));
   HIPCHK(dalloc(&a.ho, nsrc));
+  HIPCHK(dalloc(&a.sig, nsrc));
+  HIPCHK(hipMemsetAsync(a.sig, 0, sizeof(af::InitSig) * nsrc, ctx->stream));  // no slot valid
   HIPCHK(dalloc(&a.jobs, nsrc));
   HIPCHK(dalloc(&a.dscx, nsrc));
   HIPCHK(dalloc(&a.dscz, nsrc));
@@ -671,8 +694,9 @@ static int choose_members(const alifmm_ctx* ctx, int n, int fx) {
 }
 
 // subgrid-1 source init (fmm_init_kernel) of n sources into ho (jobs: device scratch of n InitJobs)
+// sig: the slots' signatures; reused / reused_stride: where the kernel reports each skipped walk
 static int launch_source_init(alifmm_ctx* ctx, int n, const double* scx, const double* scz, af::InitJob* djobs,
-                              af::HandoverOut* ho) {
+                              af::HandoverOut* ho, af::InitSig* sig, int* reused, int reused_stride) {
   std::vector<af::InitJob> jobs(n);
   for (int i = 0; i < n; i++) {
     jobs[i].isx = (long)std::nearbyint((scx[i] - ctx->gox) / ctx->dnx);
@@ -680,13 +704,14 @@ static int launch_source_init(alifmm_ctx* ctx, int n, const double* scx, const d
     jobs[i].dnx = ctx->dnx;
     jobs[i].dnz = ctx->dnz;
     jobs[i].exact_r = ctx->exact_r;
+    jobs[i].tab_epoch = ctx->tab_epoch;
     jobs[i].tstop = ctx->exact_r * ctx->dnx / ctx->vmax;
     if (jobs[i].isx < 0 || jobs[i].isx >= ctx->nx0 || jobs[i].isz < 0 || jobs[i].isz >= ctx->nz0)
       return fail(ctx, ALIFMM_E_ARG, "source %d (%g, %g) outside the grid", i, scx[i], scz[i]);
   }
   af::DevModel M = dev_model(ctx);
   HIPCHK(hipMemcpyAsync(djobs, jobs.data(), sizeof(af::InitJob) * n, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(af_launch_init(&M, djobs, n, ho, ctx->stream));
+  HIPCHK(af_launch_init(&M, djobs, n, ho, sig, ctx->init_reuse, reused, reused_stride, ctx->stream));
   return ALIFMM_OK;
 }
 
@@ -711,7 +736,7 @@ static const int kRetryCoop = -100;
 // one chunk of sources; returns ALIFMM_E_CAPACITY when a work list overflowed
 static int travel_chunk(alifmm_ctx* ctx, int sg, int n, const double* scx, const double* scz, int first_slot, int fz,
                         int fx, float* ms_init, float* ms_band, const af::HandoverOut* pre_ho = nullptr,
-                        StreamOut* so = nullptr) {
+                        StreamOut* so = nullptr, int* init_reused = nullptr) {
   const long cells = (long)fz * fx;
   long capL = std::min(cells, std::max(65536L, cells / 8) * ctx->cap_scale);
   long capC = capL;
@@ -843,7 +868,10 @@ static int travel_chunk(alifmm_ctx* ctx, int sg, int n, const double* scx, const
     if (pre_ho) {  // initialised by the travel call for all its chunks (alifmm_travel)
       P.ho = const_cast<af::HandoverOut*>(pre_ho);
     } else {
-      if ((rc = launch_source_init(ctx, n, scx, scz, a.jobs, a.ho))) return rc;
+      // (a.srcs is uploaded above, on this stream: the kernel's word lands in the copy read back below)
+      if ((rc = launch_source_init(ctx, n, scx, scz, a.jobs, a.ho, a.sig, &a.srcs[0].init_reused,
+                                   (int)(sizeof(af::BandSrc) / sizeof(int)))))
+        return rc;
       P.ho = a.ho;
       ctx->ho_last = a.ho;
       ctx->n_ho_last = n;
@@ -892,6 +920,7 @@ static int travel_chunk(alifmm_ctx* ctx, int sg, int n, const double* scx, const
   }
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
   if (fs != ctx->stream) HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_fill, 0));
+  HIPCHK(hipEventRecord(ctx->ev[4], ctx->stream));  // ev[1] .. ev[4]: the fill not hidden by the source init
   HIPCHK(hipMemsetAsync(a.kx, 0, sizeof(af::KX) * n, ctx->stream));
   HIPCHK(af_launch_band_k(&P, ctx->stream));
   // the copy team takes the tiles as they arrive; joined on every return path below
@@ -926,6 +955,11 @@ static int travel_chunk(alifmm_ctx* ctx, int sg, int n, const double* scx, const
   (void)hipEventElapsedTime(&t2, ctx->ev[1], ctx->ev[2]);
   *ms_init += t1;
   *ms_band += t2;
+  float t3 = 0;
+  (void)hipEventElapsedTime(&t3, ctx->ev[1], ctx->ev[4]);
+  ctx->t_fill_wait += t3;
+  if (init_reused)  // walks this chunk's own init launch skipped
+    for (int i = 0; i < n; i++) *init_reused += hs[i].init_reused;
   int cap_err = 0;
   for (int i = 0; i < n; i++) {
     Field& f = ctx->fields[first_slot + i];
@@ -978,16 +1012,25 @@ static int travel_impl(alifmm_ctx* ctx, int subgrid, int nsrc, const double* scx
     }
     dfree(ctx->ho_all);
     dfree(ctx->jobs_all);
+    dfree(ctx->sig_all);
+    dfree(ctx->reused_all);
     ctx->ho_all = nullptr;
     ctx->jobs_all = nullptr;
+    ctx->sig_all = nullptr;
+    ctx->reused_all = nullptr;
     ctx->n_all = 0;
     HIPCHK(dalloc(&ctx->ho_all, nsrc));
     HIPCHK(dalloc(&ctx->jobs_all, nsrc));
+    HIPCHK(dalloc(&ctx->sig_all, nsrc));
+    HIPCHK(dalloc(&ctx->reused_all, nsrc));
+    HIPCHK(hipMemsetAsync(ctx->sig_all, 0, sizeof(af::InitSig) * nsrc, ctx->stream));  // no slot valid
     ctx->n_all = nsrc;
   }
   ctx->t_stream_tail = 0;
   ctx->stream_fallback = 0;
   ctx->exact_redo = 0;
+  ctx->init_reused = 0;
+  ctx->t_fill_wait = 0;
   HIPCHK(hipEventRecord(ctx->ev[3], ctx->stream));
   // the call's timing events, destroyed on every return path
   struct Ev {
@@ -1002,10 +1045,13 @@ static int travel_impl(alifmm_ctx* ctx, int subgrid, int nsrc, const double* scx
   const af::HandoverOut* pre = nullptr;
   if (pre_init) {
     HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-    int rc = launch_source_init(ctx, nsrc, scx, scz, ctx->jobs_all, ctx->ho_all);
+    int rc = launch_source_init(ctx, nsrc, scx, scz, ctx->jobs_all, ctx->ho_all, ctx->sig_all, ctx->reused_all, 1);
     if (rc) return rc;
     HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
-    HIPCHK(hipEventSynchronize(ctx->ev[1]));
+    std::vector<int> skipped(nsrc);  // read back before the wait this path already makes
+    HIPCHK(hipMemcpyAsync(skipped.data(), ctx->reused_all, sizeof(int) * nsrc, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int v : skipped) ctx->init_reused += v;
     float t = 0;
     (void)hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]);
     ms_init += t;
@@ -1020,14 +1066,17 @@ static int travel_impl(alifmm_ctx* ctx, int subgrid, int nsrc, const double* scx
     so.dst = dsts ? dsts + s0 : nullptr;
     so.n = n;
     StreamOut* sop = dsts ? &so : nullptr;
+    // walks skipped by the chunk's first launch (a retry finds the hand-overs that launch wrote)
+    int skipped = 0, skipped_retry = 0;
+    const long cap0 = ctx->cap_scale;
     for (;;) {
       rc = travel_chunk(ctx, subgrid, n, scx + s0, scz + s0, first_slot + s0, fz, fx, &ms_init, &ms_band,
-                        pre ? pre + s0 : nullptr, sop);
+                        pre ? pre + s0 : nullptr, sop, ctx->cap_scale == cap0 ? &skipped : &skipped_retry);
       if (rc == kRetryCoop) {  // once, gang-scheduled
         const int c0 = ctx->coop;
         ctx->coop = 1;
         rc = travel_chunk(ctx, subgrid, n, scx + s0, scz + s0, first_slot + s0, fz, fx, &ms_init, &ms_band,
-                          pre ? pre + s0 : nullptr, sop);
+                          pre ? pre + s0 : nullptr, sop, &skipped_retry);
         ctx->coop = c0;
         if (rc == kRetryCoop) rc = ALIFMM_E_KERNEL;
       }
@@ -1035,6 +1084,7 @@ static int travel_impl(alifmm_ctx* ctx, int subgrid, int nsrc, const double* scx
       ctx->cap_scale *= 4;  // retry the chunk with larger work lists
     }
     if (rc) return rc;
+    ctx->init_reused += skipped;
     if (dsts) {  // fields not streamed (or a tile that never arrived): through the pinned staging ring
       for (int i = 0; i < n; i++) {
         if (so.active && !so.missing[i].load()) continue;

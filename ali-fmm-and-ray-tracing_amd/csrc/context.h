@@ -43,6 +43,7 @@ struct Arena {  // per-chunk scratch, reused across calls
   int* Ss = nullptr;
   af::BandSrc* srcs = nullptr;
   af::HandoverOut* ho = nullptr;
+  af::InitSig* sig = nullptr;  // a signature per slot of ho, allocated and zeroed with it
   af::InitJob* jobs = nullptr;
   double* dscx = nullptr;
   double* dscz = nullptr;
@@ -53,7 +54,7 @@ struct alifmm_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t fill = nullptr;  // field initialisation, overlapped with the source-init kernel
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // [4]: after the wait for the fill stream
   hipEvent_t ev_fill = nullptr;
   std::string err;
   // model
@@ -96,7 +97,19 @@ struct alifmm_ctx {
   // subgrid-1 source init of a whole multi-launch travel call (one init launch for every chunk)
   af::HandoverOut* ho_all = nullptr;
   af::InitJob* jobs_all = nullptr;
+  af::InitSig* sig_all = nullptr;  // a signature per slot of ho_all, allocated and zeroed with it
+  int* reused_all = nullptr;       // per source of that launch: its walk was skipped
   int n_all = 0;
+  // reuse of source-init hand-overs (fmm_shared.h InitSig): "init_reuse", "init_reused" (sources of
+  // the last travel call whose walk was skipped)
+  int init_reuse = 1;
+  int init_reused = 0;
+  // host copy of the small tables the walk reads (group and phase tables, the unique stiffness
+  // rows in their order): set_model bumps tab_epoch when they differ byte for byte from the last
+  // model's, so a signature of another epoch never matches
+  unsigned tab_epoch = 0;
+  int h_ncol = 0;
+  std::vector<double> h_gtab, h_ptab, h_stab;
   const af::HandoverOut* ho_last = nullptr;  // what alifmm_init_profile reads (last travel call)
   int n_ho_last = 0;
   int prof = 0;
@@ -111,6 +124,7 @@ struct alifmm_ctx {
   std::vector<Field> fields;
   Arena arena;
   double t_init = 0, t_band = 0, t_total = 0;
+  double t_fill_wait = 0;  // last travel: ms the band launches waited for the fill stream after the source init ("fill_wait_ms")
   double t_ray_kernel = 0, t_ray_pack = 0, t_find_rays = 0, t_take_rays = 0;  // last find_rays / take_rays (ms)
   int last_ray_lanes = 0;  // lanes per ray of the last find_rays launch (rays.hip af_ray_group_lanes)
   // packed points of the last alifmm_find_rays(ray_xy = NULL, ray_xy_cap = ALIFMM_KEEP_RAYS) call,

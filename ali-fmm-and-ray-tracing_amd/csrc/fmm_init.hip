@@ -17,6 +17,7 @@
 #include "local_ops.h"
 #include "kernels.h"
 #include "fields.h"
+#include "init_sig.h"
 
 namespace af {
 
@@ -667,13 +668,82 @@ AF_DEV void main_prefix(Heap& h, const DevModel& M, const InitJob& J, int wz0, i
   }
 }
 
+// ---- reuse of a slot's hand-over (fmm_shared.h InitSig) ----
+static_assert(kInitSigMaxCells <= kHandoverMax, "InitSig has room for the largest window");
+// what the walk depends on beside the model's values: the instantiation, and which of the
+// optional arrays exist (material ids: LDSMAT's source; mslo: fouds18_A()'s slownesses)
 template <bool LDSMAT>
-__global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* jobs, int njobs, HandoverOut* out) {
+AF_DEV int sig_inst(const DevModel& M) {
+  return 1 | (LDSMAT ? 2 : 0) | (M.mid ? 4 : 0) | (M.mslo ? 8 : 0);
+}
+// the material of coarse cell c as the walk resolves it (init_mat / cell_mat before any view's
+// quantisation, which is a function of these)
+template <bool LDSMAT>
+AF_DEV void sig_mat(const DevModel& M, const InitLds* L, long c, long long& veln, long long& vm, int& velpn,
+                    int& sidx) {
+  if (LDSMAT) {
+    const MatRec m = L->mat[M.mid8 ? (int)gld(M.mid8 + c) : gld(M.mid + c)];
+    veln = __double_as_longlong(m.veln);
+    vm = __double_as_longlong(m.vm);
+    velpn = m.velpn;
+    sidx = m.sidx;
+  } else {
+    veln = __double_as_longlong(gld(M.veln + c));
+    vm = __double_as_longlong(gld(M.vm + c));
+    velpn = gld(M.velpn + c);
+    sidx = M.sidx ? gld(M.sidx + c) : -1;
+  }
+}
+// All lanes (uniform): true when the slot's stored signature equals this launch's, byte for byte,
+// and its hand-over is good: the walk would reproduce it.
+template <bool LDSMAT>
+AF_DEV bool sig_equal(const DevModel& M, const InitLds* L, const InitJob& J, const InitSigWin& w, const InitSig* G,
+                      const HandoverOut* O, int lane, int nl) {
+  bool same = w.n > 0 && G->valid == 1 && O->err == 0 && G->inst == sig_inst<LDSMAT>(M) && G->nz0 == M.nz0 &&
+              G->nx0 == M.nx0;
+  const long long* a = reinterpret_cast<const long long*>(&G->job);
+  const long long* b = reinterpret_cast<const long long*>(&J);
+  for (int k = 0; k < (int)(sizeof(InitJob) / 8); k++) same = same && a[k] == b[k];
+  if (same)
+    for (int k = lane; k < w.n; k += nl) {
+      long long veln, vm;
+      int velpn, sidx;
+      sig_mat<LDSMAT>(M, L, init_sig_cell(w, k, M.nx0), veln, vm, velpn, sidx);
+      same = same && G->veln[k] == veln && G->vm[k] == vm && G->velpn[k] == velpn && G->sidx[k] == sidx;
+    }
+  return !__syncthreads_or(!same);
+}
+// All lanes: this launch's signature into the slot (valid stays 0 until the hand-over is written)
+template <bool LDSMAT>
+AF_DEV void sig_store(const DevModel& M, const InitLds* L, const InitJob& J, const InitSigWin& w, InitSig* G, int lane,
+                      int nl) {
+  if (lane == 0) {
+    G->inst = sig_inst<LDSMAT>(M);
+    G->nz0 = M.nz0;
+    G->nx0 = M.nx0;
+    G->job = J;
+  }
+  for (int k = lane; k < w.n; k += nl) {
+    long long veln, vm;
+    int velpn, sidx;
+    sig_mat<LDSMAT>(M, L, init_sig_cell(w, k, M.nx0), veln, vm, velpn, sidx);
+    G->veln[k] = veln;
+    G->vm[k] = vm;
+    G->velpn[k] = velpn;
+    G->sidx[k] = sidx;
+  }
+}
+
+// sig: one signature per slot of out, or null (no reuse, nothing recorded); reuse: 0 walks every
+// source and leaves its slot without a valid signature; reused: null, or a word per source
+// (reused[src * reused_stride]) that is set to 1 when the walk was skipped, else 0
+template <bool LDSMAT>
+__global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* jobs, int njobs, HandoverOut* out,
+                                                       InitSig* sig, int reuse, int* reused, int reused_stride) {
   __shared__ InitLds lds;
   InitLds* L = &lds;
   const int src = blockIdx.x;
   crm::lds_init();
-  if (src < njobs && threadIdx.x < 16) out[src].prof[threadIdx.x] = 0;
   DevModel M = M0;
   if (LDSMAT) {
     for (int k = threadIdx.x; k < M.nmat; k += blockDim.x) L->mat[k] = M.mtab[k];
@@ -692,6 +762,27 @@ __global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* job
   const int nnz = M.nz0, nnx = M.nx0;
   const long isx = J.isx, isz = J.isz;
   HandoverOut* O = out + src;
+  // ---- the slot already holds this walk's result: leave it (profile words included) ----
+  InitSig* G = sig ? sig + src : nullptr;
+  bool sign = false;  // this walk's signature is stored: valid is set once the hand-over is written
+  bool hit = false;
+  if (G) {
+    if (reuse) {
+      const InitSigWin w = init_sig_window(isz, isx, J.exact_r, nnz, nnx);
+      __syncthreads();  // L->mat
+      hit = sig_equal<LDSMAT>(M, L, J, w, G, O, lane, nl);
+      if (!hit) {
+        if (lane == 0) G->valid = 0;
+        sig_store<LDSMAT>(M, L, J, w, G, lane, nl);
+        sign = w.n > 0;
+      }
+    } else if (lane == 0) {
+      G->valid = 0;
+    }
+  }
+  if (reused && lane == 0) reused[(long)src * reused_stride] = hit;
+  if (hit) return;
+  if (lane < 16) O->prof[lane] = 0;
 
   const int sgs[3] = {27, 9, 3}, sizes[3] = {2, 6, 13};
   int pisz = 0, pisx = 0, pnz = 0, pnx = 0;
@@ -846,6 +937,7 @@ __global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* job
 #endif
         O->n = n;
         O->err = err;
+        if (sign && !err) G->valid = 1;
       }
       return;
     }
@@ -870,16 +962,20 @@ __global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* job
 #endif
     O->n = n;
     O->err = err;
+    if (sign && !err) G->valid = 1;
   }
 }
 
 }  // namespace af
 
 extern "C" hipError_t af_launch_init(const af::DevModel* M, af::InitJob* jobs, int njobs, af::HandoverOut* out,
+                                     af::InitSig* sig, int reuse, int* reused, int reused_stride,
                                      hipStream_t stream) {
   if (M->mid && M->nmat <= af::kInitMat)
-    hipLaunchKernelGGL(af::fmm_init_kernel<true>, dim3(njobs), dim3(128), 0, stream, *M, jobs, njobs, out);
+    hipLaunchKernelGGL(af::fmm_init_kernel<true>, dim3(njobs), dim3(128), 0, stream, *M, jobs, njobs, out, sig,
+                       reuse, reused, reused_stride);
   else
-    hipLaunchKernelGGL(af::fmm_init_kernel<false>, dim3(njobs), dim3(128), 0, stream, *M, jobs, njobs, out);
+    hipLaunchKernelGGL(af::fmm_init_kernel<false>, dim3(njobs), dim3(128), 0, stream, *M, jobs, njobs, out, sig,
+                       reuse, reused, reused_stride);
   return hipGetLastError();
 }

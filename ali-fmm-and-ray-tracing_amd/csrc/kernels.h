@@ -57,6 +57,8 @@ struct BandSrc {
   long long lsum[3];
   long long lmax;
   long long sub[4];
+  int init_reused;  // mode 0: fmm_init_kernel left this source's hand-over as it was (InitSig); it
+                    // writes this word when the chunk's own launch initialises the source
 };
 
 struct BandParams {
@@ -208,7 +210,10 @@ struct SolveVecs {
 }  // namespace af
 
 extern "C" {
-hipError_t af_launch_init(const af::DevModel* M, af::InitJob* jobs, int njobs, af::HandoverOut* out, hipStream_t stream);
+// sig: a signature per slot of out (null: none); reuse: skip the walk of a slot whose signature matches;
+// reused[i * reused_stride] (null: none): 1 when source i's walk was skipped, else 0
+hipError_t af_launch_init(const af::DevModel* M, af::InitJob* jobs, int njobs, af::HandoverOut* out, af::InitSig* sig,
+                          int reuse, int* reused, int reused_stride, hipStream_t stream);
 hipError_t af_launch_exact(const af::BandParams* P, hipStream_t stream);
 hipError_t af_launch_exact_lds(const af::BandParams* P, hipStream_t stream);
 int af_exact_lds_fits(int sg, int exact_r);  // fmm_exact_lds holds the stage grids of subgrid sg

@@ -67,7 +67,13 @@ int alifmm_set_model(alifmm_ctx* ctx, int nnz, int nnx, const double* veln, cons
  * 1.4 x the band width in force from 768 cells (0.7 at 0.5); a value set is never narrower than
  * the band width in force; cdelta_far 0 = one width everywhere), "far_sg" (the largest subgrid the
  * far band applies to, default 1), "stream_out" (subgrid-1 travels
- * with a host destination stream the fields out of the band kernel, alifmm_travel_into; default 1). */
+ * with a host destination stream the fields out of the band kernel, alifmm_travel_into; default 1),
+ * "init_reuse" (subgrid 1; default 1: a source whose initialisation would read exactly what the
+ * initialisation that last filled its slot read — the same node, spacings, exact_r, stop time,
+ * grid shape and velocity tables, and bit-identical materials in every cell within
+ * max(exact_r + 6, 16) cells of it — is not initialised again: its hand-over to the band kernel is
+ * still in device memory.  Decided on the device by comparing those inputs byte for byte, so the
+ * fields never change; 0: every source is initialised on every call). */
 int alifmm_set_option(alifmm_ctx* ctx, const char* name, double value);
 /* Read an option, or "last_k" (workgroups per source of the last band launch), "n_cu"
  * (compute units of the device), "cdelta" / "cdelta_far" (the widths in force for the resident
@@ -76,7 +82,10 @@ int alifmm_set_option(alifmm_ctx* ctx, const char* name, double value);
  * covers T <= exact_r * dnx / vmax), "stream_tail_ms" and "stream_fallback" (last travel with a host
  * destination: ms from the band kernel's end to the last streamed tile copied; fields copied after
  * the launch instead of streamed), "exact_redo" (last travel, subgrid > 1: sources the LDS exact
- * walk handed to the HBM walk), "nmat" (distinct material records of the model; 0 when there are
+ * walk handed to the HBM walk), "init_reused" (last travel, subgrid 1: sources whose
+ * initialisation was skipped under "init_reuse"; read-only), "fill_wait_ms" (last travel: ms its
+ * band launches waited, after the source initialisation, for the working fields' fills on the
+ * second stream — what a skipped initialisation no longer hides), "nmat" (distinct material records of the model; 0 when there are
  * more than the id table holds), "ray_lanes" (lanes per ray of the last find_rays launch: 9, 16, 32
  * or 64). */
 int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value);
@@ -159,7 +168,9 @@ int alifmm_band_profile(alifmm_ctx* ctx, int slot, int64_t* out14);
 int alifmm_band_span(alifmm_ctx* ctx, int slot, int64_t* out2);
 /* Source-init profile of source i of the last travel chunk (subgrid 1): wall-clock ticks
  * (100 MHz) of stage 1, 2, 3 and the exact main-loop prefix, their heap pops, the ticks the
- * relaxation role was busy in each, and their relaxations | fouds18_A() fallbacks << 32. */
+ * relaxation role was busy in each, and their relaxations | fouds18_A() fallbacks << 32.
+ * For a source whose initialisation was skipped (option "init_reuse") this is the profile of the
+ * walk that produced its hand-over, in whichever earlier call that ran. */
 int alifmm_init_profile(alifmm_ctx* ctx, int i, int64_t* out16);
 
 /* Upload a host travel-time field (fine grid of `subgrid`) into a slot, e.g. for find_ray() on a

@@ -11,6 +11,8 @@ import _alifmm  # noqa: E402
 import workloads as W  # noqa: E402
 
 ctx = _alifmm.Context(0)
+# the walk is what is measured: every source initialised on every call, the warm-up's hand-overs not reused
+ctx.set_option("init_reuse", 0)
 vt = W.default_table()
 ctx.set_model(*W.weldlike_model(), vt, vt, W.weldlike_dnx())
 scx, scz, _ = W.c5_transducers()

@@ -20,11 +20,23 @@ PH = ["p1_x1", "accept_rim", "claim", "evaluate", "fallback", "commit"]
 SUB = ["x1_wait", "rim_read", "xcd_local_frac", "drain"]
 
 
+def opt(ctx, name):
+    """An option of the last call, None with a library (ALIFMM_LIB) that does not have it."""
+    try:
+        return round(ctx.get_option(name), 3)
+    except _alifmm.AlifmmError:
+        return None
+
+
 def main():
     name = sys.argv[1]
     sizes = [int(a) for a in sys.argv[2:]] or [128, 16]
     ctx = _alifmm.Context(0)
     # ALIFMM_OPT_<NAME>=value options are applied by _alifmm.Context itself
+    # the init time is the walk's: the warm-up's hand-overs are not reused, unless
+    # ALIFMM_OPT_INIT_REUSE=1 asks for the steady state of repeated calls
+    if "ALIFMM_OPT_INIT_REUSE" not in os.environ and opt(ctx, "init_reuse") is not None:
+        ctx.set_option("init_reuse", 0)
     vt = W.default_table()
     ctx.set_model(*W.weldlike_model(), vt, vt, W.weldlike_dnx())
     sx, sz = W.c4_sources(128)
@@ -55,6 +67,7 @@ def main():
         prof.update({"live_mean": round(p[6] / st, 1), "acc_mean": round(p[7] / st, 1), "claimed_mean": round(p[8] / st, 1),
                      "close_hi_max": int(p[9]), "steps": st})
         out[str(ns)] = {"k": int(ctx.get_option("last_k")), "band_ms": round(best, 1), "init_ms": round(ti, 1),
+                        "init_reused": opt(ctx, "init_reused"), "fill_wait_ms": opt(ctx, "fill_wait_ms"),
                         "fields": h.hexdigest()[:16], "span": span, "us_per_step": prof}
     print(json.dumps(out), flush=True)
     ctx.close()

@@ -28,6 +28,7 @@ def main():
     veln, velpn, vm, sd = W.weld_model()
     vt = W.default_table()
     ctx = _alifmm.Context(0)
+    ctx.set_option("init_reuse", 0)  # (subgrid 1 only: nothing of the warm-up is reused at any subgrid)
     ctx.set_model(veln, velpn, vm, sd, vt, vt, 2e-4)
     sx, sz = W.weld_transducers()
     rx, rz = sx[31:], sz[31:]
