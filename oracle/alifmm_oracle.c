@@ -135,6 +135,7 @@ typedef struct {
     int32_t *btg;      /* heap: btg[2*k] = iz, btg[2*k+1] = ix, k >= 1 */
     long ntr;
     long maxbt;
+    long peak;         /* most heap entries held at once (band_model.c reports it) */
 } fstate_t;
 
 static inline int32_t ST(const fstate_t *f, long z, long x) {
@@ -153,6 +154,7 @@ static int addtree(fstate_t *f, long iz, long ix) {
     long nnx = f->nnx;
     f->ntr += 1;
     if (f->ntr >= f->maxbt) return -1;
+    if (f->ntr > f->peak) f->peak = f->ntr;
     f->nsts[iz * nnx + ix] = (int32_t)f->ntr;
     f->btg[2 * f->ntr + 1] = (int32_t)ix;
     f->btg[2 * f->ntr] = (int32_t)iz;
@@ -921,6 +923,7 @@ static int fstate_alloc(fstate_t *f, int nnz, int nnx, long maxbt, double *ttn_e
     f->maxbt = maxbt;
     f->btg = (int32_t *)calloc((size_t)maxbt * 2, sizeof(int32_t));
     f->ntr = 0;
+    f->peak = 0;
     if (!f->ttn || !f->nsts || !f->btg) return -1;
     for (size_t i = 0; i < n; i++) f->nsts[i] = -1;
     return 0;

@@ -256,3 +256,126 @@ int oband_travel(double scx, double scz, int nnz, int nnx, const double *veln, c
     (void)have_b;
     return 0;
 }
+
+/* travel_finer_grid() as the device runs it (api.cpp travel_chunk, sg > 1): the reference's two
+ * heap stages (x9, x3) and the heap-ordered prefix of the fine main loop (fmm_exact.hip /
+ * fmm_exact_lds.hip), then the band (fmm_band_k.hip mode 1) on the fine view, then / sg
+ * (scale_kernel).  The stages and the hand-overs are travel_finer_impl()'s, unchanged.
+ *
+ * Where the device's rule decides:
+ *  - tstop = (size2 + exact_r) dnx / vmax (api.cpp:893-894) with the COARSE dnx; the walk stops
+ *    before popping a root with key >= tstop (fmm_exact.hip:188), also at exact_r 0 (the device has
+ *    no "prefix off": tstop is then the stage-2 window's radius).
+ *  - the close list handed over is the heap (fmm_exact.hip:443-447; order is irrelevant to the band:
+ *    acceptance and the Jacobi evaluation do not depend on it); the written box (bbox) only limits
+ *    what the band kernel copies into its working field (fmm_band_k.hip:623-641) and has no
+ *    arithmetic effect, so the model has no counterpart of it.  The LDS walk's window
+ *    (fmm_exact_lds.hip:792-800) ends a walk that comes within 3 nodes of it with error 9, after
+ *    which the HBM walk runs the source again: both give the prefix modelled here.
+ *  - the band: delta = cdelta dnx / vmax, t0 = r0 dnx / vmax, the far band with
+ *    delta_far = cdelta_far dnx / vmax past tfar = r_far dnx / vmax only when both are > 0
+ *    (fmm_band_k.hip:675-678; api.cpp:835 passes cdelta_far 0 when sg > far_sg: the caller's rule),
+ *    update() with the coarse dnx, fouds18_A() with the coarse dnx / dnz, on the quantised fine view.
+ *  - the source must lie on the coarse grid (api.cpp:882-884): -2 otherwise.
+ * info[6]: band steps, nodes the prefix popped, close nodes handed over, peak heap entries of
+ * stage 1, stage 2 and the prefix. */
+int oband_travel_finer(double scx, double scz, int nz0, int nx0, const double *veln, const int64_t *velpn,
+                       const double *vel_map, const int64_t *stif, const double *av_, const double *ph_, int ncol,
+                       int sg_, double gox, double goz, double dnx, double dnz, double cdelta, double vmax,
+                       double r0, double exact_r, double cdelta_far, double r_far, double *out, long *info) {
+    long sg = sg_;
+    if (sg < 1 || sg % 2 == 0) return -3;
+    base_t bb;
+    if (make_base(&bb, nz0, nx0, veln, velpn, vel_map, stif)) return -1;
+    const mat_t *coarse = &bb.m;
+    table_t tav = {av_, ncol}, tph = {ph_, ncol};
+    const table_t *av = &tav, *ph = &tph;
+    long csx = pyround((scx - gox) / dnx), csz = pyround((scz - goz) / dnz);
+    if (csx < 0 || csx >= nx0 || csz < 0 || csz >= nz0) { free_base(&bb); return -2; }
+    view_t vf;
+    if (make_view(&vf, coarse, 0, coarse->nnz - 1, 0, coarse->nnx - 1, sg)) { free_base(&bb); return -1; }
+    int64_t *zero_stif = NULL;
+    if (coarse->stif == NULL) { /* stif_den0 is None -> zeros (:2159-2160) */
+        zero_stif = (int64_t *)calloc((size_t)nz0 * nx0 * 5, sizeof(int64_t));
+        vf.m.stif = zero_stif;
+    }
+    const mat_t *fine = &vf.m;
+    long nnz = fine->nnz, nnx = fine->nnx;
+    long isx = sg * csx, isz = sg * csz;
+    int rc = 0;
+
+    /* ---- stage 1: x9 ---- */
+    long size1 = 2 * sg + (sg - 1) / 2, s1 = 9;
+    long side1 = (s1 - 1) / 2 + s1 * ((sg - 1) / 2);
+    long left = imax(0, isx - size1), right = imin(nnx - 1, isx + size1);
+    long bottom = imax(0, isz - size1), top = imin(nnz - 1, isz + size1);
+    view_t v1;
+    fstate_t f1;
+    if (make_view(&v1, fine, bottom, top, left, right, s1)) return -1;
+    if (fstate_alloc(&f1, v1.m.nnz, v1.m.nnx, 0, NULL)) return -1;
+    long isx_1 = s1 * (isx - left), isz_1 = s1 * (isz - bottom);
+    double dnx1 = dnx / s1;
+    straight_rays(&f1, isz_1, isx_1, side1, dnx1, fine, (int)isz, (int)isx, av, 1);
+    add_edges(&f1, isz_1, isx_1, side1);
+    loopcfg_t c1 = {av, ph, dnx1, dnx1, 1, (int)isx_1, (int)isz_1, (int)(s1 * size1), 0, 0.0};
+    if (fmm_loop(&f1, &v1.m, &c1)) rc = -1;
+    long peak1 = f1.peak;
+
+    /* ---- stage 2: x3 ---- */
+    long size2 = size1 + 3 * sg, s2 = 3;
+    left = imax(0, isx - size2); right = imin(nnx - 1, isx + size2);
+    bottom = imax(0, isz - size2); top = imin(nnz - 1, isz + size2);
+    view_t v2;
+    fstate_t f2;
+    if (make_view(&v2, fine, bottom, top, left, right, s2)) return -1;
+    if (fstate_alloc(&f2, v2.m.nnz, v2.m.nnx, 0, NULL)) return -1;
+    long isx_2 = s2 * (isx - left), isz_2 = s2 * (isz - bottom);
+    double dnx2 = dnx / s2;
+    if (!rc && handover(&f1, isz_1, isx_1, &f2, isz_2, isx_2)) rc = -1;
+    loopcfg_t c2 = {av, ph, dnx2, dnx2, 1, (int)isx_2, (int)isz_2, (int)(s2 * size2), 0, 0.0};
+    if (!rc && fmm_loop(&f2, &v2.m, &c2)) rc = -1;
+    long peak2 = f2.peak;
+    fstate_free(&f1, 1);
+    free_view(&v1);
+
+    /* ---- fine grid: hand-over and the heap-ordered prefix ---- */
+    size_t n = (size_t)nnz * nnx;
+    fstate_t f;
+    memset(out, 0, n * sizeof(double));
+    if (fstate_alloc(&f, (int)nnz, (int)nnx, 0, out)) return -1;
+    if (!rc && handover(&f2, isz_2, isx_2, &f, isz, isx)) rc = -1;
+    fstate_free(&f2, 1);
+    free_view(&v2);
+    long known0 = 0, known1 = 0;
+    for (size_t i = 0; i < n; i++) known0 += f.nsts[i] == 0;
+    loopcfg_t c = {av, ph, dnx, dnz, 0, 0, 0, 0, 0, 0.0};
+    loopcfg_t ce = c;
+    ce.tstop = ((double)size2 + exact_r) * dnx / vmax;
+    if (!rc && fmm_loop(&f, fine, &ce)) rc = -1;
+    for (size_t i = 0; i < n; i++) known1 += f.nsts[i] == 0;
+
+    /* ---- heap state -> band state (known, close = in the heap, far), then the band ---- */
+    bstate_t bm;
+    if (bstate_alloc(&bm, (int)nnz, (int)nnx, out)) return -1;
+    for (size_t i = 0; i < n; i++) {
+        if (f.nsts[i] == 0) bm.f.nsts[i] = S_KNOWN;
+        else if (f.nsts[i] > 0) push_close(&bm, (long)i);
+    }
+    long nclose = bm.nL, peakp = f.peak;
+    fstate_free(&f, 0);
+    int far = r_far > 0 && cdelta_far > 0;
+    long steps = 0;
+    if (!rc)
+        steps = band_run(&bm, fine, &c, cdelta * dnx / vmax, 1, r0 * dnx / vmax, cdelta_far * dnx / vmax,
+                         far ? r_far * dnx / vmax : 0.0);
+    bstate_free(&bm, 0);
+    for (size_t i = 0; i < n; i++) out[i] = out[i] / (double)sg;
+    free_view(&vf);
+    free(zero_stif);
+    free_base(&bb);
+    if (info) {
+        info[0] = steps; info[1] = known1 - known0; info[2] = nclose;
+        info[3] = peak1; info[4] = peak2; info[5] = peakp;
+    }
+    return rc;
+}

@@ -5,6 +5,7 @@ cpu_baseline leg as the parity checker.  The product (ali-fmm-and-ray-tracing_am
 imports it.  Every function mirrors the reference function of the same name in
 /root/reference/Anis_TTF_rays.py (cited per function) with the reference's argument meaning.
 """
+import collections
 import ctypes
 import os
 import subprocess
@@ -33,8 +34,8 @@ def build():
 
 def open_lib(path):
     """A build of the restatement by its path (LIB_GLIBC, LIB_CR), loaded once per process: several
-    builds can be used side by side by passing the result as `lib=` to time_between_points and
-    find_ray_walked.  lib() stays the default one (ALIFMM_ORACLE_LIB, else LIB_GLIBC)."""
+    builds can be used side by side by passing the result as `lib=` to travel, travel_finer_grid,
+    time_between_points, find_ray_walked, band_travel and band_travel_finer.  lib() stays the default one (ALIFMM_ORACLE_LIB, else LIB_GLIBC)."""
     path = os.path.abspath(path)
     if path not in _libs:
         if not os.path.exists(path):
@@ -59,6 +60,15 @@ def open_lib(path):
         L.oref_group_vel.argtypes = [_d, _l, _l, _l, _l, _l, _d]
         L.oref_find_ray_walked.restype = _l
         L.oref_find_ray_walked.argtypes = L.oref_find_ray.argtypes + [_p]
+        # the band model (band_model.c)
+        L.oband_set_far.restype = None
+        L.oband_set_far.argtypes = [_d, _d]
+        L.oband_travel.restype = _i
+        L.oband_travel.argtypes = [_d, _d, _i, _i, _p, _p, _p, _p, _p, _p, _i, _d, _d, _d, _d, _d, _d, _i, _i, _d, _d,
+                                   _p, _p]
+        L.oband_travel_finer.restype = _i
+        L.oband_travel_finer.argtypes = [_d, _d, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _d, _d, _d, _d, _d, _d, _d, _d,
+                                         _d, _d, _p, _p]
         _libs[path] = L
     return _libs[path]
 
@@ -97,12 +107,15 @@ class _Model:
         self.ncol = self.av.shape[1]
 
 
-def travel(scx, scz, veln, velpn, vel_map, stif_den, avlist2, phase_vel, gox=0.0, goz=0.0, dnx=1e-3, dnz=None):
-    """travel() Anis_TTF_rays.py:1463-2117 (fresh zero ttn; padded stage-1 semantics)."""
+def travel(scx, scz, veln, velpn, vel_map, stif_den, avlist2, phase_vel, gox=0.0, goz=0.0, dnx=1e-3, dnz=None,
+           lib=None):
+    """travel() Anis_TTF_rays.py:1463-2117 (fresh zero ttn; padded stage-1 semantics).
+    lib: a build from open_lib() (default: lib())."""
     m = _Model(veln, velpn, vel_map, stif_den, avlist2, phase_vel)
     dnz = dnx if dnz is None else dnz
     out = np.zeros((m.nnz, m.nnx))
-    rc = lib().oref_travel(scx, scz, m.nnz, m.nnx, _ptr(m.veln), _ptr(m.velpn), _ptr(m.vel_map), _ptr(m.stif),
+    L = lib if lib is not None else globals()["lib"]()
+    rc = L.oref_travel(scx, scz, m.nnz, m.nnx, _ptr(m.veln), _ptr(m.velpn), _ptr(m.vel_map), _ptr(m.stif),
                            _ptr(m.av), _ptr(m.ph), m.ncol, gox, goz, dnx, dnz, _ptr(out))
     if rc:
         raise RuntimeError("oracle travel failed rc=%d" % rc)
@@ -110,13 +123,15 @@ def travel(scx, scz, veln, velpn, vel_map, stif_den, avlist2, phase_vel, gox=0.0
 
 
 def travel_finer_grid(scx, scz, veln, velpn, vel_map, stif_den, subgrid_size, avlist2, phase_vel, gox=0.0, goz=0.0,
-                      dnx=1e-3, dnz=None):
-    """travel_finer_grid() Anis_TTF_rays.py:2120-2832 (returns ttn / subgrid_size)."""
+                      dnx=1e-3, dnz=None, lib=None):
+    """travel_finer_grid() Anis_TTF_rays.py:2120-2832 (returns ttn / subgrid_size).
+    lib: a build from open_lib() (default: lib())."""
     m = _Model(veln, velpn, vel_map, stif_den, avlist2, phase_vel)
     dnz = dnx if dnz is None else dnz
     sg = int(subgrid_size)
     out = np.zeros((sg * (m.nnz - 1) + 1, sg * (m.nnx - 1) + 1))
-    rc = lib().oref_travel_finer_grid(scx, scz, m.nnz, m.nnx, _ptr(m.veln), _ptr(m.velpn), _ptr(m.vel_map),
+    L = lib if lib is not None else globals()["lib"]()
+    rc = L.oref_travel_finer_grid(scx, scz, m.nnz, m.nnx, _ptr(m.veln), _ptr(m.velpn), _ptr(m.vel_map),
                                       _ptr(m.stif), sg, _ptr(m.av), _ptr(m.ph), m.ncol, gox, goz, dnx, dnz,
                                       _ptr(out))
     if rc:
@@ -228,21 +243,45 @@ def group_vel(angle, c_22, c_23, c_33, c_44, sigma, vel_scale=1):
 
 
 def band_travel(scx, scz, veln, velpn, vel_map, stif_den, avlist2, phase_vel, vmax, cdelta=0.25, exact_init=False,
-                sweeps=1, r0=0.0, exact_r=0.0, gox=0.0, goz=0.0, dnx=1e-3, dnz=None, cdelta_far=0.0, r_far=0.0):
+                sweeps=1, r0=0.0, exact_r=0.0, gox=0.0, goz=0.0, dnx=1e-3, dnz=None, cdelta_far=0.0, r_far=0.0,
+                lib=None):
     """CPU model of the MI355X band-synchronous formulation (oracle/band_model.c). Returns (T, steps[4]).
-    cdelta_far / r_far: the device's optional wider band far from the source (0: off)."""
+    cdelta_far / r_far: the device's optional wider band far from the source (0: off).
+    lib: a build from open_lib() (default: lib())."""
     m = _Model(veln, velpn, vel_map, stif_den, avlist2, phase_vel)
     dnz = dnx if dnz is None else dnz
     out = np.zeros((m.nnz, m.nnx))
     steps = np.zeros(4, dtype=np.int64)
-    L = lib()
-    L.oband_set_far.argtypes = [_d, _d]
+    L = lib if lib is not None else globals()["lib"]()
     L.oband_set_far(float(cdelta_far), float(r_far))
-    L.oband_travel.restype = _i
-    L.oband_travel.argtypes = [_d, _d, _i, _i, _p, _p, _p, _p, _p, _p, _i, _d, _d, _d, _d, _d, _d, _i, _i, _d, _d, _p, _p]
     rc = L.oband_travel(scx, scz, m.nnz, m.nnx, _ptr(m.veln), _ptr(m.velpn), _ptr(m.vel_map), _ptr(m.stif),
                         _ptr(m.av), _ptr(m.ph), m.ncol, gox, goz, dnx, dnz, cdelta, vmax, int(exact_init),
                         int(sweeps), float(r0), float(exact_r), _ptr(out), _ptr(steps))
     if rc:
         raise RuntimeError("band model failed rc=%d" % rc)
     return out, steps
+
+
+FinerInfo = collections.namedtuple("FinerInfo", "steps pops close peak1 peak2 peakp")
+
+
+def band_travel_finer(scx, scz, veln, velpn, vel_map, stif_den, subgrid_size, avlist2, phase_vel, vmax, cdelta=0.5,
+                      r0=40.0, exact_r=20, cdelta_far=0.0, r_far=0.0, gox=0.0, goz=0.0, dnx=1e-3, dnz=None, lib=None):
+    """CPU model of the device's travel_finer_grid (oracle/band_model.c oband_travel_finer): the
+    reference's two heap stages and the heap-ordered prefix out to (size2 + exact_r) fine nodes, the
+    band on the fine view from there, / subgrid_size.  cdelta / cdelta_far are the widths in force
+    (the caller applies band_cdelta(ctx, sg) and the far_sg rule).  Returns (T, FinerInfo): band
+    steps, nodes the prefix popped, close nodes handed to the band, peak heap entries of stage 1,
+    stage 2 and the prefix.  lib: a build from open_lib() (default: lib())."""
+    m = _Model(veln, velpn, vel_map, stif_den, avlist2, phase_vel)
+    dnz = dnx if dnz is None else dnz
+    sg = int(subgrid_size)
+    out = np.zeros((sg * (m.nnz - 1) + 1, sg * (m.nnx - 1) + 1))
+    info = np.zeros(6, dtype=np.int64)
+    L = lib if lib is not None else globals()["lib"]()
+    rc = L.oband_travel_finer(scx, scz, m.nnz, m.nnx, _ptr(m.veln), _ptr(m.velpn), _ptr(m.vel_map), _ptr(m.stif),
+                              _ptr(m.av), _ptr(m.ph), m.ncol, sg, gox, goz, dnx, dnz, float(cdelta), float(vmax),
+                              float(r0), float(exact_r), float(cdelta_far), float(r_far), _ptr(out), _ptr(info))
+    if rc:
+        raise RuntimeError("band model (finer grid) failed rc=%d" % rc)
+    return out, FinerInfo(*[int(v) for v in info])
