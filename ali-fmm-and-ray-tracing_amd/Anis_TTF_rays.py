@@ -387,6 +387,7 @@ class ALI_FMM:
         self.ray_paths_x = self.ray_paths_y = self.ray_len = None
         self.rays = None  # RayStore of the last find_all_TTF_rays* call (compact layout)
         self.last_timing = None  # time split of the last find_all_TTF_rays* call
+        self.skip_slots = None  # device slots of the last skip_fields() call (direct and reflected fields)
         self._ctxs = {}
         self._comms = {}  # device tuple -> _alifmm.Comm (result_return = "rccl")
 
@@ -590,8 +591,44 @@ class ALI_FMM:
         res = self._fields(veln, velpn, vel_map, stif_den, subgrid_size, [source_i], [0])
         return res[source_i][2]
 
+    def skip_fields(self, reflector_iz, reflector_ix, sources=None, copy_out=False, veln=None, velpn=None,
+                    vel_map=None, stif_den=None):
+        """Reflected ("skip") travel-time fields of the elements: element -> reflector -> pixel, the
+        first arrival of that path (no counterpart in the reference).
+
+        The elements' direct fields are computed as tfm() computes them and stay on the device; the
+        reflected field of an element is then the field seeded on the reflector nodes
+        (reflector_iz[k], reflector_ix[k]) with the element's direct times there
+        (_alifmm.Context.travel_seeded(from_slots=...): read on the device, one call for all
+        elements), in slots the direct fields do not occupy.  sources: element indices into scx, scz
+        (default: all).  Subgrid 1, device 0.  Seeds plus their neighbours must fit 11 881 entries: a
+        back wall on the grid's last row of up to 5940 nodes.  A reflector given two nodes thick (the
+        wall's row and the row before it) continues the incident front without the one-layer start's
+        bias of a third of a cell's time.
+        self.skip_slots = {"direct": {element: slot}, "skip": {element: slot}} names the slots.
+        Returns the reflected fields (len(sources), nnz, nnx) with copy_out, else None."""
+        veln = self.veln if veln is None else veln
+        velpn = self.velpn if velpn is None else velpn
+        vel_map = self.vel_map if vel_map is None else vel_map
+        if vel_map is None:
+            vel_map = np.ones(np.shape(veln))
+        stif_den = self.stif_den if stif_den is None else stif_den
+        idx = list(range(self.nsrc)) if sources is None else [int(i) for i in sources]
+        for i in idx:
+            if not 0 <= i < self.nsrc:
+                raise IndexError("skip_fields: element %d of %d" % (i, self.nsrc))
+        if len(set(idx)) != len(idx):
+            raise ValueError("skip_fields: an element is listed twice")
+        res = self._fields(veln, velpn, vel_map, stif_den, 1, idx, [0], copy_out=False)
+        direct = [res[i][1] for i in idx]
+        first = max(direct) + 1 if direct else 0
+        out = self._ctx(0).travel_seeded(reflector_iz, reflector_ix, from_slots=direct, first_slot=first,
+                                         copy_out=copy_out)
+        self.skip_slots = {"direct": dict(zip(idx, direct)), "skip": {i: first + k for k, i in enumerate(idx)}}
+        return out
+
     def tfm(self, fmc, fs, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1, veln=None,
-            velpn=None, vel_map=None, stif_den=None):
+            velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct", reflector=None):
         """Total-focusing-method image of full-matrix-capture data fmc[(a, b, t)] with the
         first-arrival travel-time fields as delay laws: I(p) = sum_ab w_ab s_ab(T_a(p) + T_b(p))
         (no counterpart in the reference, whose fields exist for this purpose).
@@ -603,6 +640,12 @@ class ALI_FMM:
         The fields of the union of the elements are computed and left on the device, the
         delay-and-sum reads them there (_alifmm.Context.tfm), and only the image comes back:
         float64 (niz, nix), or complex128 for complex data.
+
+        tx_path, rx_path: "direct" (the element's first-arrival field) or "skip" (its reflected
+        field off `reflector` = (iz, ix) node arrays, skip_fields(): half-skip imaging with one side
+        "skip", full-skip with both); "skip" requires reflector and subgrid_size 1.  A skip image
+        costs two field passes on every call, also with both paths "skip": the elements' direct
+        fields (the reflected ones are seeded from them), then their reflected fields.
 
         One GPU (device 0) only: every GPU would need every field, and sharding the pixels over
         GPUs is not implemented."""
@@ -617,11 +660,25 @@ class ALI_FMM:
         for i in tx + rx:
             if not 0 <= i < self.nsrc:
                 raise IndexError("tfm: element %d of %d" % (i, self.nsrc))
+        for p in (tx_path, rx_path):
+            if p not in ("direct", "skip"):
+                raise ValueError("tfm: path %r is neither 'direct' nor 'skip'" % (p,))
         union = sorted(set(tx) | set(rx))
-        res = self._fields(veln, velpn, vel_map, stif_den, subgrid_size, union, [0], copy_out=False)
-        slot = {i: res[i][1] for i in union}
-        return self._ctx(0).tfm([slot[i] for i in tx], [slot[i] for i in rx], fmc, fs, t0=t0, weights=weights,
-                                window=window, step=step, subgrid=int(subgrid_size))
+        if "skip" in (tx_path, rx_path):
+            if reflector is None:
+                raise ValueError("tfm: the path 'skip' needs reflector=(iz, ix)")
+            if int(subgrid_size) != 1:
+                raise ValueError("tfm: the path 'skip' is defined at subgrid_size 1 only")
+            self.skip_fields(reflector[0], reflector[1], sources=union, veln=veln, velpn=velpn, vel_map=vel_map,
+                             stif_den=stif_den)
+            slots = self.skip_slots
+            txs = [slots[tx_path][i] for i in tx]
+            rxs = [slots[rx_path][i] for i in rx]
+        else:
+            res = self._fields(veln, velpn, vel_map, stif_den, subgrid_size, union, [0], copy_out=False)
+            txs, rxs = [res[i][1] for i in tx], [res[i][1] for i in rx]
+        return self._ctx(0).tfm(txs, rxs, fmc, fs, t0=t0, weights=weights, window=window, step=step,
+                                subgrid=int(subgrid_size))
 
     def plot_phase(self, material_index=1):
         import matplotlib.pyplot as plt

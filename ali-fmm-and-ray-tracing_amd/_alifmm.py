@@ -69,6 +69,7 @@ def _load():
             "alifmm_field_shape": (_i, [_p, _i, _p, _p]),
             "alifmm_travel": (_i, [_p, _i, _i, _p, _p, _i, _p]),
             "alifmm_travel_into": (_i, [_p, _i, _i, _p, _p, _i, _p]),
+            "alifmm_travel_seeded": (_i, [_p, _i, _i, _p, _p, _p, _p, _i, _p]),
             "alifmm_get_field": (_i, [_p, _i, _p]),
             "alifmm_release_fields": (_i, [_p]),
             "alifmm_copy_fields": (_i, [_p, _i, _i, _p, _i, _p]),
@@ -290,6 +291,33 @@ class Context:
         ptrs = (ctypes.c_void_p * max(1, len(rows)))(*[base + r * step for r in rows])
         self._chk(lib().alifmm_travel_into(self._h, int(subgrid), len(scx), _ptr(scx), _ptr(scz), int(first_slot),
                                            ptrs), "travel_into")
+
+    def travel_seeded(self, seed_iz, seed_ix, times=None, from_slots=None, first_slot=0, copy_out=True):
+        """Subgrid-1 travel-time fields from seed nodes (seed_iz[k], seed_ix[k]) with given times
+        (alifmm_travel_seeded): reflected legs and fronts that are no points.
+
+        times: (nseed,) for one field or (nfield, nseed) host times; or from_slots: resident
+        subgrid-1 slots, field i taking its seed times from field from_slots[i] at the seed nodes, on
+        the device.  Exactly one of the two.  The seeds keep their times; the fields land in slots
+        first_slot.. and stay resident.  Seeds plus their non-seed 4-neighbours must fit 11 881
+        entries.  Returns (nfield, nnz, nnx), or None with copy_out=False."""
+        iz, ix = _ci32(np.atleast_1d(seed_iz)), _ci32(np.atleast_1d(seed_ix))
+        if iz.ndim != 1 or iz.shape != ix.shape:
+            raise ValueError("seed_iz and seed_ix must be one-dimensional and of one length")
+        t = fs = None
+        nfield = 1  # neither source of times: the library refuses the call
+        if times is not None:
+            t = np.atleast_2d(_c64(times))
+            if t.ndim != 2 or t.shape[1] != len(iz):
+                raise ValueError("times must have shape (nseed,) or (nfield, nseed)")
+            nfield = t.shape[0]
+        if from_slots is not None:
+            fs = _ci32(np.atleast_1d(from_slots))
+            nfield = len(fs) if times is None else nfield
+        out = np.empty((nfield,) + tuple(self.shape)) if copy_out and self.shape is not None and nfield else None
+        self._chk(lib().alifmm_travel_seeded(self._h, nfield, len(iz), _ptr(iz), _ptr(ix), _ptr(t), _ptr(fs),
+                                             int(first_slot), _ptr(out)), "travel_seeded")
+        return out
 
     def get_field(self, slot, subgrid):
         fz, fx = self.field_shape(subgrid)

@@ -22,6 +22,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/alifmm.h"
@@ -273,6 +274,9 @@ int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   ctx->sig_all = nullptr;
   ctx->reused_all = nullptr;
   ctx->ho_last = nullptr;
+  dfree(ctx->seed.ho); dfree(ctx->seed.cell); dfree(ctx->seed.close); dfree(ctx->seed.win); dfree(ctx->seed.t);
+  dfree(ctx->seed.from);
+  ctx->seed = alifmm_ctx::SeedBufs();
   free_ray_bufs(ctx);
   dfree(ctx->tfm.fmc); dfree(ctx->tfm.w); dfree(ctx->tfm.tab); dfree(ctx->tfm.img);
   ctx->tfm = alifmm_ctx::TfmBufs();
@@ -368,6 +372,11 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "tfm_upload_ms")) *value = ctx->t_tfm_upload;
   else if (!strcmp(name, "tfm_kernel_ms")) *value = ctx->t_tfm_kernel;
   else if (!strcmp(name, "tfm_chunk")) *value = ctx->tfm_chunk;
+  // last alifmm_travel_seeded call: the seed pass (uploads and fmm_seed_kernel, HIP events, ms), the
+  // seeds and the close cells handed over per field
+  else if (!strcmp(name, "seed_ms")) *value = ctx->t_seed;
+  else if (!strcmp(name, "seed_nodes")) *value = (double)ctx->seed_nodes;
+  else if (!strcmp(name, "seed_close")) *value = (double)ctx->seed_close;
   // last alifmm_ray_sens call: host -> device copies (host clock, ms), the count and fill kernels
   // (HIP events, ms), the entries (row_ptr[nrays])
   else if (!strcmp(name, "sens_upload_ms")) *value = ctx->t_sens_upload;
@@ -610,11 +619,22 @@ static int ensure_arena(alifmm_ctx* ctx, int nsrc, long cells, long scells, long
   if (a.nsrc >= nsrc && a.cells >= cells && a.scells >= scells && a.capL >= capL && a.capC >= capC &&
       a.capS >= capS && a.K >= K && a.capR >= capR && a.ecells >= ecells && a.tbc >= tbc && a.sbc >= sbc)
     return ALIFMM_OK;
-  if (ctx->ho_last == a.ho) {  // init profile of a chunk whose arena goes away
-    ctx->ho_last = nullptr;
-    ctx->n_ho_last = 0;
-  }
+  // the source-init hand-overs, their signatures and jobs are no part of what a launch's geometry
+  // sizes: they stay as they are (ensure_handover sizes them, for source-init launches only), so
+  // that a launch of another size, member count or capacity — a seeded call's between two travel
+  // calls — leaves what init_reuse vouches for and what alifmm_init_profile reads
+  af::HandoverOut* const keep_ho = a.ho;
+  af::InitSig* const keep_sig = a.sig;
+  af::InitJob* const keep_jobs = a.jobs;
+  const int keep_n = a.nho;
+  a.ho = nullptr;
+  a.sig = nullptr;
+  a.jobs = nullptr;
   free_arena(a);
+  a.ho = keep_ho;
+  a.sig = keep_sig;
+  a.jobs = keep_jobs;
+  a.nho = keep_n;
   a.nsrc = nsrc;
   a.cells = cells;
   a.scells = scells;
@@ -641,12 +661,32 @@ static int ensure_arena(alifmm_ctx* ctx, int nsrc, long cells, long scells, long
     HIPCHK(dalloc(&a.Ss, (size_t)nsrc * 2 * capS));
   }
   HIPCHK(dalloc(&a.srcs, nsrc));
-  HIPCHK(dalloc(&a.ho, nsrc));
-  HIPCHK(dalloc(&a.sig, nsrc));
-  HIPCHK(hipMemsetAsync(a.sig, 0, sizeof(af::InitSig) * nsrc, ctx->stream));  // no slot valid
-  HIPCHK(dalloc(&a.jobs, nsrc));
   HIPCHK(dalloc(&a.dscx, nsrc));
   HIPCHK(dalloc(&a.dscz, nsrc));
+  return ALIFMM_OK;
+}
+
+// hand-over slots, signatures and jobs for a source-init launch of n sources (travel_chunk's own
+// launch: subgrid 1, no hand-over made elsewhere); grown only, and only here
+static int ensure_handover(alifmm_ctx* ctx, int n) {
+  Arena& a = ctx->arena;
+  if (a.nho >= n) return ALIFMM_OK;
+  if (ctx->ho_last == a.ho) {  // init profile of a chunk whose hand-overs go away
+    ctx->ho_last = nullptr;
+    ctx->n_ho_last = 0;
+  }
+  dfree(a.ho);
+  dfree(a.sig);
+  dfree(a.jobs);
+  a.ho = nullptr;
+  a.sig = nullptr;
+  a.jobs = nullptr;
+  a.nho = 0;
+  HIPCHK(dalloc(&a.ho, n));
+  HIPCHK(dalloc(&a.sig, n));
+  HIPCHK(hipMemsetAsync(a.sig, 0, sizeof(af::InitSig) * n, ctx->stream));  // no slot valid
+  HIPCHK(dalloc(&a.jobs, n));
+  a.nho = n;
   return ALIFMM_OK;
 }
 
@@ -868,6 +908,7 @@ static int travel_chunk(alifmm_ctx* ctx, int sg, int n, const double* scx, const
     if (pre_ho) {  // initialised by the travel call for all its chunks (alifmm_travel)
       P.ho = const_cast<af::HandoverOut*>(pre_ho);
     } else {
+      if ((rc = ensure_handover(ctx, n))) return rc;
       // (a.srcs is uploaded above, on this stream: the kernel's word lands in the copy read back below)
       if ((rc = launch_source_init(ctx, n, scx, scz, a.jobs, a.ho, a.sig, &a.srcs[0].init_reused,
                                    (int)(sizeof(af::BandSrc) / sizeof(int)))))
@@ -1120,6 +1161,178 @@ int alifmm_travel_into(alifmm_ctx* ctx, int subgrid, int nsrc, const double* scx
   for (int i = 0; i < nsrc; i++)
     if (!dst[i]) return fail(ctx, ALIFMM_E_ARG, "travel_into: destination %d is null", i);
   return travel_impl(ctx, subgrid, nsrc, scx, scz, first_slot, dst);
+}
+
+extern "C" hipError_t af_launch_seed(const af::DevModel* M, int nz, int nx, double dnx, double dnz, int nfield, int nseed,
+                                     int nclose, const int* seed_cell, const int* close_cell, const int* win,
+                                     const double* seed_t, const double* const* from, af::HandoverOut* out,
+                                     hipStream_t stream);
+
+// Fields from seed nodes with given times (include/alifmm.h): the host builds the geometry the
+// fields share (close cells, their 5 x 5 windows into the seed list) and checks everything it can
+// before any launch; fmm_seed_kernel writes one hand-over per field into the context's own buffer;
+// travel_chunk runs the band from there as from a source init made elsewhere (pre_ho).
+int alifmm_travel_seeded(alifmm_ctx* ctx, int nfield, int nseed, const int32_t* seed_iz, const int32_t* seed_ix,
+                         const double* seed_t, const int32_t* from_slot, int first_slot, double* out) {
+  if (!ctx || !ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "travel_seeded: no model");
+  if (nfield < 1 || nseed < 1) return fail(ctx, ALIFMM_E_ARG, "travel_seeded: nfield %d, nseed %d", nfield, nseed);
+  if (!seed_iz || !seed_ix || first_slot < 0) return fail(ctx, ALIFMM_E_ARG, "travel_seeded: bad args");
+  if ((seed_t != nullptr) == (from_slot != nullptr))
+    return fail(ctx, ALIFMM_E_ARG, "travel_seeded: exactly one of seed_t and from_slot must be given");
+  const int nz = ctx->nz0, nx = ctx->nx0;
+  if (nz >= 32768 || nx >= 32768)
+    return fail(ctx, ALIFMM_E_ARG, "travel_seeded: field sides must stay below 32768 nodes (packed list keys)");
+  std::vector<int> cell(nseed);
+  std::unordered_map<int, int> index;  // cell -> place in the seed list
+  index.reserve((size_t)nseed * 2);
+  for (int k = 0; k < nseed; k++) {
+    if (seed_iz[k] < 0 || seed_iz[k] >= nz || seed_ix[k] < 0 || seed_ix[k] >= nx)
+      return fail(ctx, ALIFMM_E_ARG, "travel_seeded: seed %d (%d, %d) outside the %d x %d grid", k, seed_iz[k],
+                  seed_ix[k], nz, nx);
+    cell[k] = seed_iz[k] * nx + seed_ix[k];
+    if (!index.emplace(cell[k], k).second)
+      return fail(ctx, ALIFMM_E_ARG, "travel_seeded: seed %d (%d, %d) is listed twice", k, seed_iz[k], seed_ix[k]);
+  }
+  if (from_slot) {
+    for (int i = 0; i < nfield; i++) {
+      const int s = from_slot[i];
+      if (s < 0 || s >= (int)ctx->fields.size() || !ctx->fields[s].d)
+        return fail(ctx, ALIFMM_E_ARG, "travel_seeded: no field in from_slot %d", s);
+      const Field& f = ctx->fields[s];
+      if (f.sg != 1 || f.nz != nz || f.nx != nx)
+        return fail(ctx, ALIFMM_E_ARG, "travel_seeded: from_slot %d holds a %d x %d field of subgrid %d, not a subgrid-1 field of the model",
+                    s, f.nz, f.nx, f.sg);
+      if (s >= first_slot && s < first_slot + nfield)
+        return fail(ctx, ALIFMM_E_ARG, "travel_seeded: from_slot %d lies inside the destination slots %d .. %d", s,
+                    first_slot, first_slot + nfield - 1);
+    }
+  } else {
+    for (size_t k = 0; k < (size_t)nfield * nseed; k++)
+      if (!(seed_t[k] >= 0.0) || seed_t[k] == INFINITY || std::signbit(seed_t[k]))
+        return fail(ctx, ALIFMM_E_ARG, "travel_seeded: field %d, seed %d: time %g is not finite or is negative",
+                    (int)(k / nseed), (int)(k % nseed), seed_t[k]);
+  }
+  // step -1's cells: every in-grid 4-neighbour of a seed that is no seed, ascending
+  std::vector<int> close;
+  close.reserve((size_t)nseed * 2);
+  auto is_seed = [&](int z, int x) { return index.find(z * nx + x) != index.end(); };
+  for (int k = 0; k < nseed; k++) {
+    const int z = seed_iz[k], x = seed_ix[k];
+    if (x > 0 && !is_seed(z, x - 1)) close.push_back(cell[k] - 1);
+    if (x < nx - 1 && !is_seed(z, x + 1)) close.push_back(cell[k] + 1);
+    if (z > 0 && !is_seed(z - 1, x)) close.push_back(cell[k] - nx);
+    if (z < nz - 1 && !is_seed(z + 1, x)) close.push_back(cell[k] + nx);
+  }
+  std::sort(close.begin(), close.end());
+  close.erase(std::unique(close.begin(), close.end()), close.end());
+  const int nclose = (int)close.size();
+  ctx->seed_nodes = nseed;
+  ctx->seed_close = nclose;
+  if ((long)nseed + nclose > af::kHandoverMax)
+    return fail(ctx, ALIFMM_E_CAPACITY, "travel_seeded: %d seeds and %d close cells exceed the hand-over's %d entries",
+                nseed, nclose, af::kHandoverMax);
+  std::vector<int> win((size_t)nclose * 25);
+  for (int j = 0; j < nclose; j++) {
+    const int z = close[j] / nx, x = close[j] % nx;
+    for (int o = 0; o < 25; o++) {
+      const int zz = z + o / 5 - 2, xx = x + o % 5 - 2;
+      int k = -1;
+      if (zz >= 0 && zz < nz && xx >= 0 && xx < nx) {
+        auto it = index.find(zz * nx + xx);
+        if (it != index.end()) k = it->second;
+      }
+      win[(size_t)j * 25 + o] = k;
+    }
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  auto& sb = ctx->seed;
+  HIPCHK(dgrow(&sb.ho, &sb.ho_n, (size_t)nfield));
+  HIPCHK(dgrow(&sb.cell, &sb.cell_n, (size_t)nseed));
+  HIPCHK(dgrow(&sb.close, &sb.close_n, (size_t)nclose));
+  HIPCHK(dgrow(&sb.win, &sb.win_n, win.size()));
+  ctx->t_stream_tail = 0;
+  ctx->stream_fallback = 0;
+  ctx->exact_redo = 0;
+  ctx->init_reused = 0;
+  ctx->t_fill_wait = 0;
+  struct Ev {
+    hipEvent_t e = nullptr;
+    ~Ev() {
+      if (e) (void)hipEventDestroy(e);
+    }
+  } t_begin, t_end;
+  HIPCHK(hipEventCreate(&t_begin.e));
+  HIPCHK(hipEventCreate(&t_end.e));
+  HIPCHK(hipEventRecord(t_begin.e, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+  HIPCHK(hipMemcpyAsync(sb.cell, cell.data(), sizeof(int) * nseed, hipMemcpyHostToDevice, ctx->stream));
+  if (nclose > 0) {
+    HIPCHK(hipMemcpyAsync(sb.close, close.data(), sizeof(int) * nclose, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipMemcpyAsync(sb.win, win.data(), sizeof(int) * win.size(), hipMemcpyHostToDevice, ctx->stream));
+  }
+  std::vector<const double*> from;
+  if (from_slot) {
+    from.resize(nfield);
+    for (int i = 0; i < nfield; i++) from[i] = ctx->fields[from_slot[i]].d;
+    HIPCHK(dgrow(&sb.from, &sb.from_n, (size_t)nfield));
+    HIPCHK(hipMemcpyAsync(sb.from, from.data(), sizeof(double*) * nfield, hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    HIPCHK(dgrow(&sb.t, &sb.t_n, (size_t)nfield * nseed));
+    HIPCHK(hipMemcpyAsync(sb.t, seed_t, sizeof(double) * nfield * nseed, hipMemcpyHostToDevice, ctx->stream));
+  }
+  // n and err of every hand-over: zeroed before, read back after the seed pass
+  HIPCHK(hipMemset2DAsync(sb.ho, sizeof(af::HandoverOut), 0, 2 * sizeof(int), nfield, ctx->stream));
+  af::DevModel M = dev_model(ctx);
+  HIPCHK(af_launch_seed(&M, nz, nx, ctx->dnx, ctx->dnz, nfield, nseed, nclose, sb.cell, sb.close, sb.win,
+                        from_slot ? nullptr : sb.t, from_slot ? sb.from : nullptr, sb.ho, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+  std::vector<int> head(2 * (size_t)nfield);
+  HIPCHK(hipMemcpy2DAsync(head.data(), 2 * sizeof(int), sb.ho, sizeof(af::HandoverOut), 2 * sizeof(int), nfield,
+                          hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float ms_init = 0, ms_band = 0;
+  (void)hipEventElapsedTime(&ms_init, ctx->ev[0], ctx->ev[1]);
+  ctx->t_seed = ms_init;
+  for (int i = 0; i < nfield; i++) {
+    if (head[2 * i + 1])  // before the band launch: a negative Tmin would never accept anything
+      return fail(ctx, ALIFMM_E_ARG, "travel_seeded: field %d: a seed time read from slot %d is not finite or is negative",
+                  i, from_slot ? from_slot[i] : -1);
+    if (head[2 * i] != nseed + nclose)
+      return fail(ctx, ALIFMM_E_KERNEL, "travel_seeded: field %d: hand-over of %d entries, %d expected", i, head[2 * i],
+                  nseed + nclose);
+  }
+  // chunks, the capacity retry and the cooperative retry as alifmm_travel (travel_impl)
+  int chunk = std::max(1, std::min(ctx->batch, std::max(8, ctx->n_cu / 2 / 8 * 8)));
+  if (nfield > chunk) {
+    const int nl = (nfield + chunk - 1) / chunk;
+    chunk = std::min(chunk, ((nfield + nl - 1) / nl + 7) / 8 * 8);
+  }
+  for (int s0 = 0; s0 < nfield; s0 += chunk) {
+    const int n = std::min(chunk, nfield - s0);
+    int rc;
+    for (;;) {
+      rc = travel_chunk(ctx, 1, n, nullptr, nullptr, first_slot + s0, nz, nx, &ms_init, &ms_band, sb.ho + s0);
+      if (rc == kRetryCoop) {  // once, gang-scheduled
+        const int c0 = ctx->coop;
+        ctx->coop = 1;
+        rc = travel_chunk(ctx, 1, n, nullptr, nullptr, first_slot + s0, nz, nx, &ms_init, &ms_band, sb.ho + s0);
+        ctx->coop = c0;
+        if (rc == kRetryCoop) rc = ALIFMM_E_KERNEL;
+      }
+      if (rc != ALIFMM_E_CAPACITY || ctx->cap_scale * 4 > 64) break;
+      ctx->cap_scale *= 4;  // retry the chunk with larger work lists
+    }
+    if (rc) return rc;
+  }
+  HIPCHK(hipEventRecord(t_end.e, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float tot = 0;
+  (void)hipEventElapsedTime(&tot, t_begin.e, t_end.e);
+  ctx->t_init = ms_init;
+  ctx->t_band = ms_band;
+  ctx->t_total = tot;
+  if (out) return alifmm_copy_fields(ctx, first_slot, nfield, out, 0, nullptr);
+  return ALIFMM_OK;
 }
 
 int alifmm_get_field(alifmm_ctx* ctx, int slot, double* out) {

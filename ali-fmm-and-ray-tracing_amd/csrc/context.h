@@ -45,6 +45,8 @@ struct Arena {  // per-chunk scratch, reused across calls
   af::HandoverOut* ho = nullptr;
   af::InitSig* sig = nullptr;  // a signature per slot of ho, allocated and zeroed with it
   af::InitJob* jobs = nullptr;
+  int nho = 0;  // sources ho / sig / jobs are sized for (api.cpp ensure_handover): grown by a source-init
+                // launch alone, they outlive every regrowth of the rest (ensure_arena)
   double* dscx = nullptr;
   double* dscz = nullptr;
 };
@@ -112,6 +114,19 @@ struct alifmm_ctx {
   std::vector<double> h_gtab, h_ptab, h_stab;
   const af::HandoverOut* ho_last = nullptr;  // what alifmm_init_profile reads (last travel call)
   int n_ho_last = 0;
+  // alifmm_travel_seeded: the seeded hand-overs (a buffer of their own: the InitSig signatures vouch
+  // for ho / ho_all only) and the call's geometry and times, grow-only, freed with the context
+  struct SeedBufs {
+    af::HandoverOut* ho = nullptr;
+    int* cell = nullptr;    // seed cells, list order
+    int* close = nullptr;   // close cells, ascending
+    int* win = nullptr;     // [close][25] seed indices
+    double* t = nullptr;    // [nfield][nseed] host times
+    const double** from = nullptr;  // [nfield] source fields
+    size_t ho_n = 0, cell_n = 0, close_n = 0, win_n = 0, t_n = 0, from_n = 0;
+  } seed;
+  double t_seed = 0;                   // last alifmm_travel_seeded: the seed pass (ms)
+  long seed_nodes = 0, seed_close = 0; // its seeds and close cells
   int prof = 0;
   int coop = 1;  // band kernel: cooperative launch (1; 0 under rocprofv3) or plain launch after a residency check (0)
   int members = 0;     // band kernel: workgroups per source (0: as many as the device fits, <= 16)

@@ -87,7 +87,8 @@ int alifmm_set_option(alifmm_ctx* ctx, const char* name, double value);
  * band launches waited, after the source initialisation, for the working fields' fills on the
  * second stream — what a skipped initialisation no longer hides), "nmat" (distinct material records of the model; 0 when there are
  * more than the id table holds), "ray_lanes" (lanes per ray of the last find_rays launch: 9, 16, 32
- * or 64). */
+ * or 64), "seed_ms", "seed_nodes" and "seed_close" (last alifmm_travel_seeded: ms of its seed pass,
+ * its seeds and the close cells handed over with them). */
 int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value);
 
 /* Shape of a travel-time field for subgrid size sg: (sg*(nnz-1)+1, sg*(nnx-1)+1). */
@@ -112,6 +113,65 @@ int alifmm_travel(alifmm_ctx* ctx, int subgrid, int nsrc, const double* scx, con
  * stay resident in slots first_slot .. first_slot+nsrc-1. */
 int alifmm_travel_into(alifmm_ctx* ctx, int subgrid, int nsrc, const double* scx, const double* scz,
                        int first_slot, double* const* dst);
+
+/* Travel-time fields from a set of seed nodes with given times instead of a point source: the
+ * reflected leg of a half-skip path (the incident field's values on the reflector, frozen, and the
+ * march restarted from them: multi-stage FMM) and fronts that are no points (a plane wave: the array
+ * line seeded with the steering delays).  The reference has no counterpart.  Subgrid 1 only.
+ *   nfield             fields of the call; they land in slots first_slot .. first_slot + nfield - 1
+ *                      and stay resident, as with alifmm_travel
+ *   seed_iz, seed_ix   int32 [nseed] the seed nodes, shared by all fields
+ *   seed_t             float64 [nfield][nseed] host times, or NULL
+ *   from_slot          int32 [nfield] resident subgrid-1 fields to read the times from, or NULL:
+ *                      seed k of field i has the time field(from_slot[i])[seed_iz[k]][seed_ix[k]], read
+ *                      on the device with no host round trip (64 incident fields in, 64 reflected
+ *                      fields out, one call)
+ *   out (nullable)     float64 [nfield][nnz][nnx], copied after the launches
+ * Exactly one of seed_t and from_slot is given.
+ * 1. Seeds.  The seeds are known with their times exactly as given and are never re-evaluated
+ *    (Dirichlet values).  Any node set: one node, a line, several layers, scattered nodes.
+ * 2. Step -1.  Every in-grid 4-neighbour of a seed that is no seed becomes close.  Its value is one
+ *    band step's evaluate-and-commit with all seeds as the accepted set: update(), and where that
+ *    returns -1 the fouds18_A() fallback, Jacobi-style against the seeds-only state (every other
+ *    node far, ttn 0), with the device functions and the material path of the band kernel's
+ *    evaluate phase.
+ * 3. Hand-over and band run.  The hand-over lists the seeds in list order as known, then the close
+ *    cells in ascending cell index iz * nnx + ix: its order is a function of the node list alone.
+ *    The band kernel then runs unchanged with the context's band options in force.  Its schedule (the
+ *    "r0" narrowing, the far band) is in absolute time Tmin, not in distance from the seeds: for the
+ *    reflected continuation of a point-source field that is the right measure of the front's
+ *    curvature; a front seeded at t = 0 starts with the narrowed band of a point source.
+ * 4. Capacity.  Seeds plus close cells must fit the hand-over's 11 881 entries (109 x 109), else
+ *    ALIFMM_E_CAPACITY with a message, decided on the host before any launch.  A 4096-node back wall
+ *    on the grid's last row needs 8 192 and fits; a 4096-node interior line needs 12 288 and does not
+ *    (seed it in pieces of other calls' fields, or coarser); more entries are not supported.
+ * 5. Errors.  ALIFMM_E_ARG with a message, the context staying usable, when: the context has no
+ *    model; nfield < 1 or nseed < 1; a node is outside the grid or listed twice; both or neither of
+ *    seed_t and from_slot are given; a from_slot is empty, not of subgrid 1, of another shape, or
+ *    inside the destination range; a seed time, host or gathered, is not finite or is negative (the
+ *    sign bit set: -0.0 too).  A negative Tmin makes the band width negative and nothing is ever
+ *    accepted, and the band kernel's edge buffers encode known-ness in the sign of -t; gathered
+ *    times are checked on the device, before the band launch.
+ * 6. Untouched state.  The seeded hand-overs live in a buffer of their own: the signatures of
+ *    "init_reuse" and the hand-overs they vouch for are not touched (a travel call repeated after a
+ *    seeded call skips its walks as if nothing had happened in between), alifmm_init_profile keeps
+ *    reporting source-init walks only, and the from_slot fields and every slot outside the
+ *    destination range are not modified.
+ * 7. Around the call.  Chunking by "batch", the work-list capacity retry, "members", "stripe_log",
+ *    "xcd_local", alifmm_source_stats, alifmm_band_profile and alifmm_last_timing work as for
+ *    alifmm_travel; init_ms is then the seed pass.  The fields are bit-identical for every member
+ *    count and chunking, and a field does not depend on the other fields of its call.
+ * 8. alifmm_get_option: "seed_ms" (uploads and the seed kernel of the last call), "seed_nodes" and
+ *    "seed_close" (its seeds and close cells, set also when the call fails with ALIFMM_E_CAPACITY).
+ * 9. A seed layer one node thick.  From a flat isotropic front given on one row, fouds18_A() finds
+ *    three collinear known nodes and gives the next row t + (2/3) dnz / v (t + dnz / v next to the
+ *    side columns, where it sees fewer): the one-layer start is early by a third of a cell's time,
+ *    once — 8e-5 of a 4096-cell path, inside the project's 1.4e-3 field envelope.  A consistent layer
+ *    two nodes thick continues a plane front exactly (to 1e-15).  Give two layers where they exist
+ *    (the reflector row and the row before it, both read from the incident field).  The operators
+ *    are the reference's and are not altered. */
+int alifmm_travel_seeded(alifmm_ctx* ctx, int nfield, int nseed, const int32_t* seed_iz, const int32_t* seed_ix,
+                         const double* seed_t, const int32_t* from_slot, int first_slot, double* out);
 
 /* Copy a resident field to the host; release all resident fields. */
 int alifmm_get_field(alifmm_ctx* ctx, int slot, double* out);
