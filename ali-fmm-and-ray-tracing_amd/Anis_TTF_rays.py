@@ -859,6 +859,74 @@ class ALI_FMM:
             stif_den = np.zeros((veln.shape[0], veln.shape[1], 5), dtype=np.int64)
         return self._rays(veln, velpn, vel_map, stif_den, subgrid_size, trans_pairs, save_rays, n_threads, True)
 
+    def find_all_skip_rays(self, veln, velpn, vel_map=None, reflector=None, subgrid_size=1, trans_pairs=None,
+                           stif_den=None, save_rays=True):
+        """Back-wall echo paths between the transducer pairs, for an array on one face: element i ->
+        reflector -> element j, the first reflected arrival (no counterpart in the reference, whose
+        find_all_TTF_rays traces straight through the part between facing arrays).
+
+        reflector = (iz, ix): the reflector's nodes on the model grid (scaled by subgrid_size here);
+        any node set.  trans_pairs: (n, n), 1 marks a pair; default every pair i <= j, pulse-echo
+        (i == j) included.  The fields of the union of the pairs' elements are computed once and left
+        on device 0; per pair the node with the least T_i + T_j is picked on the device
+        (_alifmm.Context.skip_rays), the two legs are traced back from it and joined i .. hit .. j.
+        Returns times (n, n): the joined rays' times.  self.skip_pick_times (n, n) holds the picks'
+        field times T_i + T_j (inf where there is no hit, nan for pairs not asked for) and
+        self.skip_hits (n, n) the picked node's index into `reflector` (-1: none or not asked for).
+        With save_rays the rays go to self.rays (a RayStore sized for joined rays), so ray_path,
+        ray_sensitivity, tomography_step and save_ray_store work on echo paths as on direct ones.
+        One GPU only (device 0)."""
+        if reflector is None:
+            raise ValueError("find_all_skip_rays: reflector=(iz, ix) is required")
+        if type(vel_map) == type(None):
+            vel_map = np.ones(veln.shape)
+        if type(stif_den) == type(None):
+            stif_den = np.zeros((veln.shape[0], veln.shape[1], 5), dtype=np.int64)
+        n_trans = len(self.isx)
+        sg = int(subgrid_size)
+        w_iz = sg * np.asarray(reflector[0], dtype=np.int64).ravel()
+        w_ix = sg * np.asarray(reflector[1], dtype=np.int64).ravel()
+        if trans_pairs is None:
+            trans_pairs = np.triu(np.ones((n_trans, n_trans)))
+        trans_pairs = np.asarray(trans_pairs)
+        ii, jj = np.nonzero(trans_pairs == 1)
+        times = np.zeros((n_trans, n_trans))
+        self.skip_pick_times = np.full((n_trans, n_trans), np.nan)
+        self.skip_hits = np.full((n_trans, n_trans), -1, dtype=np.int64)
+        self.skip_flags = np.zeros((n_trans, n_trans), dtype=np.int32)  # the joined rays' flags (8: no hit)
+        max_pts = 2 * 5 * (veln.shape[0] + veln.shape[1]) - 1
+        store = RayStore(n_trans, max_pts) if save_rays else None
+        if len(ii):
+            elements = sorted(set(ii.tolist()) | set(jj.tolist()))
+            res = self._fields(veln, velpn, vel_map, stif_den, sg, elements, [0], copy_out=False)
+            slot = np.zeros(n_trans, dtype=np.int32)
+            for e in elements:
+                slot[e] = res[e][1]
+            ctx = self._ctx(0)
+            a_xy = np.stack([sg * self.isx[ii], sg * self.isz[ii]], axis=1)
+            b_xy = np.stack([sg * self.isx[jj], sg * self.isz[jj]], axis=1)
+            pick, hit, t, lens, flags, pts = ctx.skip_rays(slot[ii], slot[jj], a_xy, b_xy, w_iz, w_ix,
+                                                           with_points=save_rays)
+            for _ in range(int(np.count_nonzero(flags & 1))):
+                print(_EARLY_MSG)
+            times[ii, jj] = t
+            self.skip_pick_times[ii, jj] = pick
+            self.skip_hits[ii, jj] = hit
+            self.skip_flags[ii, jj] = flags
+            if save_rays:
+                store.add(ii, jj, lens, pts if sg == 1 else pts / sg)
+        if save_rays:
+            self.rays = store
+            self.ray_len = store.ray_len
+            self._ray_model = (veln, velpn, vel_map, stif_den)
+            if n_trans * n_trans * max_pts * 8 <= ray_dense_limit_bytes:
+                self.ray_paths_x = store.dense(0)
+                self.ray_paths_y = store.dense(1)
+            else:
+                self.ray_paths_x = PackedRayPaths(store, 0)
+                self.ray_paths_y = PackedRayPaths(store, 1)
+        return times
+
     def ray_path(self, i, j):
         """Ray (i, j) from the last find_all_TTF_rays* call (reference :4687-4705)."""
         if self.ray_len[i, j] == 0:

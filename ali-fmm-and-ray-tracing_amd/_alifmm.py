@@ -32,6 +32,7 @@ class RayCapacityError(AlifmmError, IndexError):
 
 # ray flags (kernels.h RayParams::flags)
 RAY_EARLY_EXIT, RAY_CAPACITY, RAY_BAD_PLANE = 1, 2, 4
+RAY_NO_HIT = 8  # alifmm_skip_rays: no reflector node with a finite time sum (the ray is empty)
 
 
 def check_ray_flags(flags):
@@ -75,6 +76,8 @@ def _load():
             "alifmm_copy_fields": (_i, [_p, _i, _i, _p, _i, _p]),
             "alifmm_find_rays": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _l]),
             "alifmm_take_rays": (_i, [_p, _p, _l, _p]),
+            "alifmm_skip_pick": (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p]),
+            "alifmm_skip_rays": (_i, [_p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _l]),
             "alifmm_source_stats": (_i, [_p, _i, _p, _p]),
             "alifmm_last_timing": (_i, [_p, _p, _p, _p]),
             "alifmm_band_profile": (_i, [_p, _i, _p]),
@@ -454,6 +457,61 @@ class Context:
             rays.append((p[:, 0].copy(), p[:, 1].copy()))
             off += lens[k]
         return times, lens, flags, rays
+
+    @staticmethod
+    def _skip_request(slots_a, slots_b, w_iz, w_ix):
+        sa, sb = _ci32(np.atleast_1d(slots_a)), _ci32(np.atleast_1d(slots_b))
+        iz, ix = _ci32(np.atleast_1d(w_iz)), _ci32(np.atleast_1d(w_ix))
+        if sa.ndim != 1 or sa.shape != sb.shape:
+            raise ValueError("slots_a and slots_b must be one-dimensional and of one length")
+        if iz.ndim != 1 or iz.shape != ix.shape:
+            raise ValueError("w_iz and w_ix must be one-dimensional and of one length")
+        return sa, sb, iz, ix
+
+    def skip_pick(self, slots_a, slots_b, w_iz, w_ix):
+        """The first back-wall echo of element pairs (alifmm_skip_pick): for pair k the reflector node
+        q with the least finite T_a + T_b of the resident fields slots_a[k], slots_b[k] at the nodes
+        (w_iz[q], w_ix[q]) of their fine grid; of equal sums the lowest q.
+        Returns (pick_time float64, hit int32): hit -1 and pick_time +inf where no sum is finite."""
+        sa, sb, iz, ix = self._skip_request(slots_a, slots_b, w_iz, w_ix)
+        n = len(sa)
+        pick, hit = np.full(n, np.inf), np.full(n, -1, dtype=np.int32)
+        self._chk(lib().alifmm_skip_pick(self._h, n, _ptr(sa), _ptr(sb), len(iz), _ptr(iz), _ptr(ix), _ptr(pick),
+                                         _ptr(hit)), "skip_pick")
+        return pick, hit
+
+    def skip_rays(self, slots_a, slots_b, a_xy, b_xy, w_iz, w_ix, with_points=True, check=True):
+        """Echo paths a -> reflector -> b (alifmm_skip_rays): the pick of skip_pick, then the two legs
+        hit -> a (through field slots_a[k]) and hit -> b (through slots_b[k]) joined into one ray
+        a .. hit .. b.  a_xy, b_xy: the elements' (x, z) on the fine grid.
+
+        Returns (pick_time, hit, times, lens, flags, points): times = t_A + t_B of the legs; flags
+        the legs' bits or'ed, RAY_NO_HIT (8) for a pair without a hit (no points); points the packed
+        (sum(lens), 2) array in pair order, or None with with_points=False.  The points wait in the
+        context as after find_rays, so ray_sens / sens_op_build with ray_xy=None called before the
+        points are taken (with_points="keep": they stay kept, points is None) read them in place.
+        check: raise (check_ray_flags) for a leg cut short."""
+        sa, sb, iz, ix = self._skip_request(slots_a, slots_b, w_iz, w_ix)
+        n = len(sa)
+        a_xy, b_xy = _c64(a_xy).reshape(n, 2), _c64(b_xy).reshape(n, 2)
+        pick, hit = np.full(n, np.inf), np.full(n, -1, dtype=np.int32)
+        times, lens, flags = np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        keep = bool(with_points) and n > 0
+        self._chk(lib().alifmm_skip_rays(self._h, n, _ptr(sa), _ptr(sb), _ptr(a_xy), _ptr(b_xy), len(iz), _ptr(iz),
+                                         _ptr(ix), _ptr(pick), _ptr(hit), _ptr(times), _ptr(lens), _ptr(flags), None,
+                                         KEEP_RAYS if keep else 0), "skip_rays")
+        if check:
+            check_ray_flags(flags)
+        if not with_points or with_points == "keep":
+            return pick, hit, times, lens, flags, None
+        npts = int(lens.sum(dtype=np.int64))
+        pts = np.empty((npts, 2))
+        if keep:
+            got = ctypes.c_int64(0)
+            self._chk(lib().alifmm_take_rays(self._h, _ptr(pts), npts, ctypes.byref(got)), "take_rays")
+            if got.value != npts:
+                raise AlifmmError("take_rays: %d points kept, %d expected" % (got.value, npts))
+        return pick, hit, times, lens, flags, pts
 
     def ray_sens(self, ray_len, ray_xy=None, subgrid=1, flags=None, weights=None, maps=True, rows=False):
         """Travel-time sensitivities along rays (alifmm_ray_sens): per piece of every ray the coarse

@@ -280,6 +280,9 @@ int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   free_ray_bufs(ctx);
   dfree(ctx->tfm.fmc); dfree(ctx->tfm.w); dfree(ctx->tfm.tab); dfree(ctx->tfm.img);
   ctx->tfm = alifmm_ctx::TfmBufs();
+  dfree(ctx->skip.tab); dfree(ctx->skip.wiz); dfree(ctx->skip.wix); dfree(ctx->skip.row); dfree(ctx->skip.hit);
+  dfree(ctx->skip.W); dfree(ctx->skip.pick);
+  ctx->skip = alifmm_ctx::SkipBufs();
   {
     auto& b = ctx->sens;
     dfree(b.xy); dfree(b.off); dfree(b.cnt); dfree(b.row); dfree(b.len); dfree(b.flags); dfree(b.status); dfree(b.w);
@@ -367,6 +370,11 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "ray_pack_ms")) *value = ctx->t_ray_pack;
   else if (!strcmp(name, "find_rays_ms")) *value = ctx->t_find_rays;
   else if (!strcmp(name, "take_rays_ms")) *value = ctx->t_take_rays;
+  // last alifmm_skip_pick / alifmm_skip_rays call (HIP events, ms): the gather and pair-reduction
+  // kernels; the join kernel, summed over the launches (skip_rays sets the ray timings above too,
+  // ray_pack_ms being 0: the join takes the packing kernel's place)
+  else if (!strcmp(name, "skip_pick_ms")) *value = ctx->t_skip_pick;
+  else if (!strcmp(name, "skip_join_ms")) *value = ctx->t_skip_join;
   // last alifmm_tfm call (ms): host -> device copies of the data, the weights and the slot table
   // (host clock); the delay-and-sum kernel (HIP events)
   else if (!strcmp(name, "tfm_upload_ms")) *value = ctx->t_tfm_upload;
@@ -1627,6 +1635,46 @@ int alifmm_last_timing(alifmm_ctx* ctx, double* init_ms, double* band_ms, double
   return ALIFMM_OK;
 }
 
+// the ray tracer's work buffers hold `rays` rays of max_pts points (kept across calls, regrown for a larger launch)
+static int ensure_ray_bufs(alifmm_ctx* ctx, int rays, int max_pts) {
+  auto& rb = ctx->rb;
+  if (rb.rays >= rays && rb.pts >= (size_t)rays * max_pts) return ALIFMM_OK;
+  free_ray_bufs(ctx);
+  HIPCHK(dalloc(&rb.rx, (size_t)rays * max_pts));
+  HIPCHK(dalloc(&rb.ry, (size_t)rays * max_pts));
+  HIPCHK(dalloc(&rb.t, rays));
+  HIPCHK(dalloc(&rb.len, rays));
+  HIPCHK(dalloc(&rb.flags, rays));
+  HIPCHK(dalloc(&rb.jobs, rays));
+  HIPCHK(dalloc(&rb.off, rays));
+  rb.rays = rays;
+  rb.pts = (size_t)rays * max_pts;
+  return ALIFMM_OK;
+}
+
+// device-kept chunks -> per-ray host staging (the kept budget is spent): the chunks hold the rays
+// ids[0], ids[1], ... in order, lens[id] points each; the chunks are freed
+static hipError_t spill_kept_rays(alifmm_ctx* ctx, const int* ids, const std::vector<int32_t>& lens,
+                                  std::vector<std::vector<double>>& staged) {
+  staged.assign(lens.size(), {});
+  size_t r = 0;
+  for (auto& k : ctx->kept_dev) {
+    std::vector<double> h(2 * (size_t)k.npts);
+    hipError_t e = hipMemcpy(h.data(), k.d, 16 * (size_t)k.npts, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    size_t o = 0;
+    while (o < (size_t)k.npts) {
+      const int id = ids[r++];
+      staged[id].assign(h.begin() + 2 * o, h.begin() + 2 * (o + lens[id]));
+      o += lens[id];
+    }
+  }
+  for (auto& k : ctx->kept_dev) dfree(k.d);
+  ctx->kept_dev.clear();
+  ctx->kept_pts = 0;
+  return hipSuccess;
+}
+
 int alifmm_find_rays(alifmm_ctx* ctx, int npairs, const int32_t* field_slot, const double* src_xy,
                      const double* rec_xy, double* times, int32_t* ray_len, int32_t* flags, double* ray_xy,
                      int64_t ray_xy_cap) {
@@ -1677,18 +1725,7 @@ int alifmm_find_rays(alifmm_ctx* ctx, int npairs, const int32_t* field_slot, con
   }
   chunk = std::min(chunk, npairs);
   auto& rb = ctx->rb;
-  if (rb.rays < chunk || rb.pts < (size_t)chunk * max_pts) {
-    free_ray_bufs(ctx);
-    HIPCHK(dalloc(&rb.rx, (size_t)chunk * max_pts));
-    HIPCHK(dalloc(&rb.ry, (size_t)chunk * max_pts));
-    HIPCHK(dalloc(&rb.t, chunk));
-    HIPCHK(dalloc(&rb.len, chunk));
-    HIPCHK(dalloc(&rb.flags, chunk));
-    HIPCHK(dalloc(&rb.jobs, chunk));
-    HIPCHK(dalloc(&rb.off, chunk));
-    rb.rays = chunk;
-    rb.pts = (size_t)chunk * max_pts;
-  }
+  if (int rc = ensure_ray_bufs(ctx, chunk, max_pts)) return rc;
   double *d_rx = rb.rx, *d_ry = rb.ry, *d_t = rb.t, *d_packed = nullptr;
   int *d_len = rb.len, *d_flags = rb.flags;
   af::RayJob* d_jobs = rb.jobs;
@@ -1728,24 +1765,8 @@ int alifmm_find_rays(alifmm_ctx* ctx, int npairs, const int32_t* field_slot, con
   size_t kept_bytes = 0;
   // device-kept chunks -> per-ray host staging (rays ids[0 .. ndone-1] of the single group, in order)
   auto spill_kept = [&](const std::vector<int>& ids) -> hipError_t {
-    staged.assign(npairs, {});
-    size_t r = 0;
-    for (auto& k : ctx->kept_dev) {
-      std::vector<double> h(2 * (size_t)k.npts);
-      hipError_t e = hipMemcpy(h.data(), k.d, 16 * (size_t)k.npts, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) return e;
-      size_t o = 0;
-      while (o < (size_t)k.npts) {
-        const int id = ids[r++];
-        staged[id].assign(h.begin() + 2 * o, h.begin() + 2 * (o + lens[id]));
-        o += lens[id];
-      }
-    }
-    for (auto& k : ctx->kept_dev) dfree(k.d);
-    ctx->kept_dev.clear();
-    ctx->kept_pts = 0;
     dev_keep = false;
-    return hipSuccess;
+    return spill_kept_rays(ctx, ids.data(), lens, staged);
   };
   for (auto& g : groups) {
     const int sg = g.first;
@@ -1895,6 +1916,299 @@ int alifmm_take_rays(alifmm_ctx* ctx, double* ray_xy, int64_t ray_xy_cap, int64_
   }
   release_kept_rays(ctx);
   return done(ALIFMM_OK);
+}
+
+// ---- back-wall echo paths between element pairs (skip_pairs.hip) ----
+// the checked request of alifmm_skip_pick / alifmm_skip_rays and its picks
+struct SkipRequest {
+  int sg = 0, fnz = 0, fnx = 0;
+  std::vector<int32_t> hit;
+  std::vector<double> pick;
+};
+
+// checks (ALIFMM_E_ARG, nothing launched), then the gather and the pair reduction; the picks on the host
+static int skip_pick_run(alifmm_ctx* ctx, const char* what, int npairs, const int32_t* slot_a, const int32_t* slot_b,
+                         int nw, const int32_t* w_iz, const int32_t* w_ix, bool rays, SkipRequest& R) {
+  if (!slot_a || !slot_b) return fail(ctx, ALIFMM_E_ARG, "%s: slot_a or slot_b is NULL", what);
+  if (!w_iz || !w_ix) return fail(ctx, ALIFMM_E_ARG, "%s: w_iz or w_ix is NULL", what);
+  // the distinct slots of the request, in order of first use: row r of W belongs to slots[r]
+  std::unordered_map<int, int> row_of;
+  std::vector<int> slots;
+  std::vector<int32_t> rows(2 * (size_t)npairs);
+  for (int k = 0; k < 2 * npairs; k++) {
+    const int s = k < npairs ? slot_a[k] : slot_b[k - npairs];
+    if (s < 0 || s >= (int)ctx->fields.size() || !ctx->fields[s].d)
+      return fail(ctx, ALIFMM_E_ARG, "%s: pair %d refers to empty slot %d", what, k % npairs, s);
+    auto it = row_of.find(s);
+    if (it == row_of.end()) {
+      it = row_of.emplace(s, (int)slots.size()).first;
+      slots.push_back(s);
+    }
+    rows[k] = it->second;
+  }
+  const Field& f0 = ctx->fields[slots[0]];
+  for (int s : slots) {
+    const Field& f = ctx->fields[s];
+    if (f.sg != f0.sg) return fail(ctx, ALIFMM_E_ARG, "%s: mixed subgrids %d and %d (slots %d and %d)", what, f0.sg, f.sg, slots[0], s);
+    if (f.nz != f0.nz || f.nx != f0.nx)
+      return fail(ctx, ALIFMM_E_ARG, "%s: mixed field shapes (slots %d and %d)", what, slots[0], s);
+  }
+  for (int q = 0; q < nw; q++)
+    if (w_iz[q] < 0 || w_iz[q] >= f0.nz || w_ix[q] < 0 || w_ix[q] >= f0.nx)
+      return fail(ctx, ALIFMM_E_ARG, "%s: reflector node %d (%d, %d) outside the %d x %d field", what, q, w_iz[q], w_ix[q],
+                  f0.nz, f0.nx);
+  if (rays && 6 * f0.sg + 3 > kMaxRayCand)
+    return fail(ctx, ALIFMM_E_ARG, "%s: subgrid %d has %d plane candidates (> %d supported)", what, f0.sg, 6 * f0.sg + 3,
+                kMaxRayCand);
+  if (slots.size() > 65535) return fail(ctx, ALIFMM_E_ARG, "%s: %zu distinct slots (> 65535)", what, slots.size());
+  R.sg = f0.sg;
+  R.fnz = f0.nz;
+  R.fnx = f0.nx;
+  HIPCHK(hipSetDevice(ctx->device));
+  alifmm_ctx::SkipBufs& B = ctx->skip;
+  const size_t np = (size_t)npairs, nf = slots.size();
+  HIPCHK(dgrow(&B.tab, &B.tab_n, nf));
+  HIPCHK(dgrow(&B.wiz, &B.wiz_n, (size_t)nw));
+  HIPCHK(dgrow(&B.wix, &B.wix_n, (size_t)nw));
+  HIPCHK(dgrow(&B.row, &B.row_n, 2 * np));
+  HIPCHK(dgrow(&B.hit, &B.hit_n, np));
+  HIPCHK(dgrow(&B.pick, &B.pick_n, np));
+  HIPCHK(dgrow(&B.W, &B.W_n, nf * (size_t)nw));
+  std::vector<const double*> tab(nf);
+  for (size_t r = 0; r < nf; r++) tab[r] = ctx->fields[slots[r]].d;
+  HIPCHK(hipMemcpyAsync(B.tab, tab.data(), nf * sizeof(double*), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(B.wiz, w_iz, (size_t)nw * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(B.wix, w_ix, (size_t)nw * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(B.row, rows.data(), 2 * np * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+  HIPCHK(af_launch_skip_pick(B.tab, (int)nf, B.wiz, B.wix, f0.nx, nw, B.W, B.row, B.row + np, npairs, B.pick, B.hit,
+                             ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+  R.hit.resize(np);
+  R.pick.resize(np);
+  HIPCHK(hipMemcpyAsync(R.hit.data(), B.hit, np * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(R.pick.data(), B.pick, np * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));  // the staging vectors above live until here
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
+  ctx->t_skip_pick = ms;
+  return ALIFMM_OK;
+}
+
+static int skip_check_counts(alifmm_ctx* ctx, const char* what, int npairs, int nw) {
+  if (!ctx) return ALIFMM_E_ARG;
+  if (!ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "%s: no model", what);
+  if (npairs < 0) return fail(ctx, ALIFMM_E_ARG, "%s: npairs %d", what, npairs);
+  if (nw < 1) return fail(ctx, ALIFMM_E_ARG, "%s: nw %d", what, nw);
+  return ALIFMM_OK;
+}
+
+int alifmm_skip_pick(alifmm_ctx* ctx, int npairs, const int32_t* slot_a, const int32_t* slot_b, int nw,
+                     const int32_t* w_iz, const int32_t* w_ix, double* pick_time, int32_t* hit) {
+  if (int rc = skip_check_counts(ctx, "skip_pick", npairs, nw)) return rc;
+  if (npairs == 0) return ALIFMM_OK;
+  if (!pick_time || !hit) return fail(ctx, ALIFMM_E_ARG, "skip_pick: pick_time or hit is NULL");
+  ctx->t_skip_pick = ctx->t_skip_join = 0;
+  SkipRequest R;
+  if (int rc = skip_pick_run(ctx, "skip_pick", npairs, slot_a, slot_b, nw, w_iz, w_ix, false, R)) return rc;
+  std::copy(R.hit.begin(), R.hit.end(), hit);
+  std::copy(R.pick.begin(), R.pick.end(), pick_time);
+  return ALIFMM_OK;
+}
+
+int alifmm_skip_rays(alifmm_ctx* ctx, int npairs, const int32_t* slot_a, const int32_t* slot_b, const double* a_xy,
+                     const double* b_xy, int nw, const int32_t* w_iz, const int32_t* w_ix, double* pick_time,
+                     int32_t* hit, double* times, int32_t* ray_len, int32_t* flags, double* ray_xy,
+                     int64_t ray_xy_cap) {
+  if (int rc = skip_check_counts(ctx, "skip_rays", npairs, nw)) return rc;
+  if (npairs == 0) return ALIFMM_OK;
+  if (!a_xy || !b_xy) return fail(ctx, ALIFMM_E_ARG, "skip_rays: a_xy or b_xy is NULL");
+  if (!times || !ray_len) return fail(ctx, ALIFMM_E_ARG, "skip_rays: times or ray_len is NULL");
+  const auto t_call = std::chrono::steady_clock::now();
+  ctx->t_skip_pick = ctx->t_skip_join = 0;
+  SkipRequest R;
+  if (int rc = skip_pick_run(ctx, "skip_rays", npairs, slot_a, slot_b, nw, w_iz, w_ix, true, R)) return rc;
+  ctx->t_ray_kernel = ctx->t_ray_pack = 0;
+  const int max_pts = 5 * (ctx->nz0 + ctx->nx0);  // per leg; a joined ray holds up to 2 max_pts - 1
+  // Pairs per launch: two legs a pair, the legs sized as alifmm_find_rays sizes its rays (wavefronts for
+  // every SIMD at the ray kernel's occupancy, the point buffers within a quarter of the free memory);
+  // 9-lane groups when the legs fill the device with them
+  const long fill9 = (long)std::max(ctx->n_cu, 1) * 4 * af_ray_waves_per_simd() * (64 / 9);
+  const int ray_packed = 2L * npairs >= fill9 ? 1 : 0;
+  const int glanes = af_ray_group_lanes(R.sg, ray_packed);
+  size_t keep_budget = SIZE_MAX;
+  int chunk = npairs;
+  {
+    const long target = (long)std::max(ctx->n_cu, 1) * 4 * af_ray_waves_per_simd() * (64 / glanes);
+    size_t free_b = 0, total_b = 0;
+    long by_mem = target;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+      by_mem = (long)(free_b / 4 / ((size_t)max_pts * 2 * sizeof(double) + 64));
+      keep_budget = free_b / 4;
+    }
+    const long cmax = std::max(1024L, std::min(target, by_mem)) / 2;
+    const long nlaunch = (npairs + cmax - 1) / cmax;
+    chunk = (int)std::min<long>((npairs + nlaunch - 1) / nlaunch, npairs);
+  }
+  auto& rb = ctx->rb;
+  if (int rc = ensure_ray_bufs(ctx, 2 * chunk, max_pts)) return rc;
+  double* d_packed = nullptr;
+  // an error return also drops the points kept so far (kept_pts then matches no ray list)
+#define SCHK(call)                                                            \
+  do {                                                                        \
+    hipError_t e_ = (call);                                                   \
+    if (e_ != hipSuccess) {                                                   \
+      dfree(d_packed);                                                        \
+      release_kept_rays(ctx);                                                 \
+      return fail(ctx, ALIFMM_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
+    }                                                                         \
+  } while (0)
+  std::vector<int32_t> lens(npairs, 0), flg(npairs, 0);
+  std::vector<double> tms(npairs, 0.0);
+  std::vector<int> ids(npairs);
+  for (int k = 0; k < npairs; k++) ids[k] = k;
+  const bool keep = !ray_xy && ray_xy_cap == ALIFMM_KEEP_RAYS;
+  // the pairs are traced in the caller's order, so kept points stay on the device, chunk after chunk
+  // (within keep_budget; past it the kept chunks move to host staging), as after alifmm_find_rays
+  bool dev_keep = keep;
+  release_kept_rays(ctx);
+  std::vector<std::vector<double>> staged(ray_xy ? npairs : 0);
+  size_t kept_bytes = 0;
+  const af::DevModel M = dev_model(ctx);
+  for (int c0 = 0; c0 < npairs; c0 += chunk) {
+    const int n = std::min(chunk, npairs - c0);
+    // the chunk's pairs with a hit: pair live[p] has legs 2 p (to a) and 2 p + 1 (to b) of the launch
+    std::vector<int> live;
+    std::vector<af::RayJob> jobs;
+    for (int i = 0; i < n; i++) {
+      const int k = c0 + i, h = R.hit[k];
+      if (h < 0) {
+        flg[k] = 8;
+        continue;
+      }
+      live.push_back(k);
+      af::RayJob J;
+      J.sx = (double)w_ix[h];
+      J.sy = (double)w_iz[h];
+      J.ttf = ctx->fields[slot_a[k]].d;
+      J.rx = a_xy[2 * k];
+      J.ry = a_xy[2 * k + 1];
+      jobs.push_back(J);
+      J.ttf = ctx->fields[slot_b[k]].d;
+      J.rx = b_xy[2 * k];
+      J.ry = b_xy[2 * k + 1];
+      jobs.push_back(J);
+    }
+    const int m = (int)live.size();
+    if (!m) continue;
+    SCHK(hipMemcpyAsync(rb.jobs, jobs.data(), sizeof(af::RayJob) * 2 * m, hipMemcpyHostToDevice, ctx->stream));
+    af::RayParams P;
+    memset(&P, 0, sizeof P);
+    P.M = M;
+    P.fnz = R.fnz;
+    P.fnx = R.fnx;
+    P.sg = R.sg;
+    P.dnx = ctx->dnx;
+    P.nrays = 2 * m;
+    P.max_pts = max_pts;
+    P.jobs = rb.jobs;
+    P.ray_x = rb.rx;
+    P.ray_y = rb.ry;
+    P.ray_len = rb.len;
+    P.times = rb.t;
+    P.flags = rb.flags;
+    P.glanes = glanes;
+    ctx->last_ray_lanes = glanes;
+    SCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+    SCHK(af_launch_rays(&P, ctx->stream));
+    SCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+    std::vector<double> t(2 * m);
+    std::vector<int> l(2 * m), fl(2 * m);
+    SCHK(hipMemcpyAsync(t.data(), rb.t, 8 * (size_t)(2 * m), hipMemcpyDeviceToHost, ctx->stream));
+    SCHK(hipMemcpyAsync(l.data(), rb.len, 4 * (size_t)(2 * m), hipMemcpyDeviceToHost, ctx->stream));
+    SCHK(hipMemcpyAsync(fl.data(), rb.flags, 4 * (size_t)(2 * m), hipMemcpyDeviceToHost, ctx->stream));
+    SCHK(hipStreamSynchronize(ctx->stream));
+    {
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]);
+      ctx->t_ray_kernel += ms;
+    }
+    std::vector<long long> off(m + 1, 0);
+    for (int p = 0; p < m; p++) {
+      const int k = live[p];
+      // a leg has at least its two end points and at most max_pts (find_ray_kernel's capacity)
+      if (l[2 * p] < 2 || l[2 * p + 1] < 2 || l[2 * p] > max_pts || l[2 * p + 1] > max_pts) {
+        dfree(d_packed);
+        release_kept_rays(ctx);
+        return fail(ctx, ALIFMM_E_KERNEL, "skip_rays: pair %d has legs of %d and %d points", k, l[2 * p], l[2 * p + 1]);
+      }
+      lens[k] = l[2 * p] + l[2 * p + 1] - 1;
+      flg[k] = fl[2 * p] | fl[2 * p + 1];
+      tms[k] = (flg[k] & 6) ? 0.0 : t[2 * p] + t[2 * p + 1];
+      off[p + 1] = off[p] + lens[k];
+    }
+    if (!(ray_xy || keep)) continue;
+    dfree(d_packed);
+    d_packed = nullptr;
+    SCHK(dalloc(&d_packed, (size_t)2 * off[m]));
+    SCHK(hipMemcpyAsync(rb.off, off.data(), 8 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+    SCHK(hipEventRecord(ctx->ev[2], ctx->stream));
+    SCHK(af_launch_skip_join(rb.rx, rb.ry, rb.len, rb.off, m, max_pts, d_packed, ctx->stream));
+    SCHK(hipEventRecord(ctx->ev[3], ctx->stream));
+    SCHK(hipEventSynchronize(ctx->ev[3]));
+    {
+      float ms = 0;
+      (void)hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]);
+      ctx->t_skip_join += ms;
+    }
+    if (dev_keep && kept_bytes + 16 * (size_t)off[m] > keep_budget) {
+      dev_keep = false;
+      SCHK(spill_kept_rays(ctx, ids.data(), lens, staged));
+    }
+    if (dev_keep) {  // the chunk's joined rays stay on the device (the context owns them now)
+      kept_bytes += 16 * (size_t)off[m];
+      ctx->kept_dev.push_back({d_packed, (int64_t)off[m]});
+      ctx->kept_pts += off[m];
+      d_packed = nullptr;
+      continue;
+    }
+    if (staged.empty()) staged.assign(npairs, {});
+    std::vector<double> packed(2 * (size_t)off[m]);
+    SCHK(hipMemcpyAsync(packed.data(), d_packed, 16 * (size_t)off[m], hipMemcpyDeviceToHost, ctx->stream));
+    SCHK(hipStreamSynchronize(ctx->stream));
+    for (int p = 0; p < m; p++) staged[live[p]].assign(packed.begin() + 2 * off[p], packed.begin() + 2 * off[p + 1]);
+  }
+#undef SCHK
+  dfree(d_packed);
+  int64_t total = 0;
+  for (int k = 0; k < npairs; k++) total += lens[k];
+  int rc = ALIFMM_OK;
+  if (ray_xy && total > ray_xy_cap)
+    rc = fail(ctx, ALIFMM_E_ARG, "skip_rays: ray_xy capacity %lld < %lld", (long long)ray_xy_cap, (long long)total);
+  if (!rc) {
+    int64_t o = 0;
+    for (int k = 0; k < npairs; k++) {
+      if (pick_time) pick_time[k] = R.pick[k];
+      if (hit) hit[k] = R.hit[k];
+      times[k] = tms[k];
+      ray_len[k] = lens[k];
+      if (flags) flags[k] = flg[k];
+      if (ray_xy) std::copy(staged[k].begin(), staged[k].end(), ray_xy + 2 * o);
+      o += lens[k];
+    }
+    if (keep && !dev_keep) {
+      if (staged.empty()) staged.assign(npairs, {});
+      ctx->kept_rays.swap(staged);
+      ctx->kept_pts = total;
+    }
+  }
+  if (rc || (dev_keep && ctx->kept_pts != total)) {
+    release_kept_rays(ctx);
+    if (!rc) rc = fail(ctx, ALIFMM_E_KERNEL, "skip_rays: kept points do not add up to the ray lengths");
+  }
+  ctx->t_find_rays = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+  if (rb.pts * 2 * sizeof(double) > kRayBufKeepBytes) free_ray_bufs(ctx);
+  return rc;
 }
 
 int alifmm_put_field(alifmm_ctx* ctx, int slot, int subgrid, const double* data) {

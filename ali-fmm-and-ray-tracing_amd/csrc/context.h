@@ -160,6 +160,15 @@ struct alifmm_ctx {
     af::RayJob* jobs = nullptr;
     long long* off = nullptr;
   } rb;
+  // alifmm_skip_pick / alifmm_skip_rays: grow-only device buffers (the distinct fields' pointer table,
+  // the reflector nodes, W[field][node], the pairs' rows of W, the picks), freed with the context
+  struct SkipBufs {
+    const double** tab = nullptr;
+    int *wiz = nullptr, *wix = nullptr, *row = nullptr, *hit = nullptr;  // row: [2][npairs]
+    double *W = nullptr, *pick = nullptr;
+    size_t tab_n = 0, wiz_n = 0, wix_n = 0, row_n = 0, hit_n = 0, W_n = 0, pick_n = 0;
+  } skip;
+  double t_skip_pick = 0, t_skip_join = 0;  // last skip_pick / skip_rays: the pick's kernels, the join kernel (ms)
   // pinned staging ring of alifmm_copy_fields (pageable destinations)
   static constexpr int kPinBufs = 4;
   static constexpr size_t kPinBytes = 32u << 20;

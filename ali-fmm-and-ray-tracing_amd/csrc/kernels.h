@@ -230,6 +230,15 @@ int af_ray_waves_per_simd();
 int af_ray_group_lanes(int sg, int packed);
 hipError_t af_launch_pack_rays(const double* rx, const double* ry, const int* len, const long long* off, int nrays,
                                int max_pts, double* packed, hipStream_t stream);
+// back-wall echo paths (skip_pairs.hip).  Pick: W[f][q] = fld[f] at node (w_iz[q], w_ix[q]) for the nfld
+// distinct fields of a request, then per pair the (value, node) minimum over W[row_a] + W[row_b].
+// Join: legs 2 p and 2 p + 1 of the ray kernel's point buffers (leg_len [2 npairs]) -> pair p's joined
+// ray at point off[p] of packed (replaces af_launch_pack_rays for such a launch)
+hipError_t af_launch_skip_pick(const double* const* fld, int nfld, const int* w_iz, const int* w_ix, int fnx, int nw,
+                               double* W, const int* row_a, const int* row_b, int npairs, double* pick_time, int* hit,
+                               hipStream_t stream);
+hipError_t af_launch_skip_join(const double* rx, const double* ry, const int* leg_len, const long long* off, int npairs,
+                               int max_pts, double* packed, hipStream_t stream);
 hipError_t af_launch_local_ops(const af::LocalOpsParams* P, hipStream_t stream);
 hipError_t af_launch_mat_slowness(const af::DevModel* M, double* out, hipStream_t stream);
 hipError_t af_launch_tbp(const af::DevModel* M, int n, const double* x1, const double* x2, const double* y1,

@@ -210,6 +210,63 @@ int alifmm_find_rays(alifmm_ctx* ctx, int npairs, const int32_t* field_slot, con
  * (the reference's dense (n, n, 5(nnz+nnx)) arrays, :4286-4289, do not fit at 4096²). */
 int alifmm_take_rays(alifmm_ctx* ctx, double* ray_xy, int64_t ray_xy_cap, int64_t* n_points);
 
+/* Back-wall echo paths between element pairs: element a -> reflector -> element b, the only
+ * arrivals that cross the part when one array sits on one face (pulse-echo: a = b).  The reference
+ * has no counterpart.  By Fermat and reciprocity the first reflected arrival is the minimum over the
+ * reflector nodes w of T_a(w) + T_b(w), the specular point w* is where it is taken, and the path is
+ * two back-traced rays, w* -> a through T_a and w* -> b through T_b, joined into one ray a .. w* .. b
+ * that alifmm_ray_sens and alifmm_sens_op_build walk as any other.
+ *
+ * alifmm_skip_pick
+ *   slot_a[k], slot_b[k]  int32 [npairs] resident fields of pair k's two elements.  Slots may repeat
+ *                      and slot_a[k] == slot_b[k] is allowed; all slots of a call hold fields of one
+ *                      subgrid and one shape
+ *   w_iz, w_ix         int32 [nw] reflector nodes on the fields' fine grid: any node set in any order;
+ *                      a node may be listed twice
+ *   pick_time, hit     float64 [npairs], int32 [npairs]
+ * For pair k and node q, s_q = T_a[w_iz[q]][w_ix[q]] + T_b[w_iz[q]][w_ix[q]] (one float64 add).  The
+ * candidates are the q whose s_q is finite (neither NaN nor +-inf).  hit[k] is the smallest q among
+ * those with the least s_q, and pick_time[k] = s_hit[k]; with no candidate hit[k] = -1 and
+ * pick_time[k] = +inf.  The result is the minimum of a total order (the sum, then the node number;
+ * -0.0 equals 0.0), so it does not depend on how the device reduces.  A pair's result depends on
+ * nothing else in the request, and the fields are not modified.  On the device one pass per distinct
+ * slot gathers its values at the nodes (a strided reflector is read once per field, not once per
+ * pair) into a grow-only buffer of the context, freed with it; one wavefront per pair reduces.
+ *
+ * alifmm_skip_rays     the pick, then two legs per pair traced by the ray kernel of alifmm_find_rays
+ *   a_xy[2k], b_xy[2k] float64 [npairs][2] the elements' (x, z) on the fields' fine grid
+ *   pick_time, hit     as above; each nullable here
+ *   times, ray_len, flags, ray_xy, ray_xy_cap   as in alifmm_find_rays, for the joined rays
+ * Leg A of pair k starts at (w_ix[hit], w_iz[hit]) with receiver a_xy[k] in field slot_a[k]; leg B
+ * starts at the same point with receiver b_xy[k] in field slot_b[k].  A leg's points, time and flag
+ * bits are those of the same job given to alifmm_find_rays, whatever the chunking and the lanes per
+ * ray.  The joined ray is leg A's points in reverse order, then leg B's from its second point on:
+ * ray_len = len_A + len_B - 1, the first point is a, the last is b, and the hit node appears once.
+ * flags = flags_A | flags_B; bit 3 (value 8): no hit — such a ray has ray_len 0 and times 0 and is
+ * not traced.  times[k] = t_A + t_B (one float64 add, in that order), 0 when flags has bit 1 or 2
+ * set, as alifmm_find_rays does for a ray cut short.  A joined ray holds up to
+ * 2 * 5 * (nnz + nnx) - 1 points.  ray_xy, ray_xy_cap, ALIFMM_KEEP_RAYS, alifmm_take_rays and the
+ * ray_xy == NULL forms of alifmm_ray_sens and alifmm_sens_op_build behave exactly as after
+ * alifmm_find_rays with the joined rays as the rays (a join kernel writes them where the packing
+ * kernel writes kept rays; the kept-point budget and its host staging are unchanged).  The 4-byte
+ * hits come to the host to make the leg jobs.
+ *
+ * Both: npairs == 0 is ALIFMM_OK.  ALIFMM_E_ARG with a message, the context staying usable, when:
+ * the context has no model; npairs < 0 or nw < 1; slot_a, slot_b, w_iz or w_ix is NULL, pick_time or
+ * hit (skip_pick), a_xy, b_xy, times or ray_len (skip_rays) is NULL; a slot is empty; the slots mix
+ * subgrids or shapes; a node lies outside the field; skip_rays: the subgrid's 6 sg + 3 plane
+ * candidates exceed what the ray kernel holds (256), or ray_xy holds fewer than the joined rays'
+ * points (nothing is written then, as with alifmm_find_rays).  One GPU.
+ * alifmm_get_option: "skip_pick_ms" (the gather and pair-reduction kernels of the last call),
+ * "skip_join_ms" (the join kernel, summed over the launches), and after alifmm_skip_rays the ray
+ * timings as after alifmm_find_rays ("ray_kernel_ms", "find_rays_ms", "ray_lanes"; "ray_pack_ms" 0). */
+int alifmm_skip_pick(alifmm_ctx* ctx, int npairs, const int32_t* slot_a, const int32_t* slot_b, int nw,
+                     const int32_t* w_iz, const int32_t* w_ix, double* pick_time, int32_t* hit);
+int alifmm_skip_rays(alifmm_ctx* ctx, int npairs, const int32_t* slot_a, const int32_t* slot_b, const double* a_xy,
+                     const double* b_xy, int nw, const int32_t* w_iz, const int32_t* w_ix, double* pick_time,
+                     int32_t* hit, double* times, int32_t* ray_len, int32_t* flags, double* ray_xy,
+                     int64_t ray_xy_cap);
+
 /* Diagnostics of the last alifmm_travel(): per slot band steps [stage1, stage2, stage3|-, main]
  * and main-grid cell-sweeps (local-operator evaluations); device time of the last call's kernels. */
 int alifmm_source_stats(alifmm_ctx* ctx, int slot, int64_t* steps4, int64_t* cell_sweeps);
