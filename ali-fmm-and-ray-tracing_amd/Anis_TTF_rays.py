@@ -627,6 +627,40 @@ class ALI_FMM:
         self.skip_slots = {"direct": dict(zip(idx, direct)), "skip": {i: first + k for k, i in enumerate(idx)}}
         return out
 
+    def _pair_slots(self, what, tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path, rx_path, reflector):
+        """The resident slots of the transmitters' and receivers' fields of tfm() and simulate_fmc()
+        (`what` names the caller in messages): their argument checks, the fields of the union of
+        the elements computed and left on the device, the skip_fields() route for "skip" paths."""
+        veln = self.veln if veln is None else veln
+        velpn = self.velpn if velpn is None else velpn
+        vel_map = self.vel_map if vel_map is None else vel_map
+        if vel_map is None:
+            vel_map = np.ones(np.shape(veln))
+        stif_den = self.stif_den if stif_den is None else stif_den
+        tx = list(range(self.nsrc)) if tx is None else [int(i) for i in tx]
+        rx = list(range(self.nsrc)) if rx is None else [int(i) for i in rx]
+        for i in tx + rx:
+            if not 0 <= i < self.nsrc:
+                raise IndexError("%s: element %d of %d" % (what, i, self.nsrc))
+        for p in (tx_path, rx_path):
+            if p not in ("direct", "skip"):
+                raise ValueError("%s: path %r is neither 'direct' nor 'skip'" % (what, p))
+        union = sorted(set(tx) | set(rx))
+        if "skip" in (tx_path, rx_path):
+            if reflector is None:
+                raise ValueError("%s: the path 'skip' needs reflector=(iz, ix)" % what)
+            if int(subgrid_size) != 1:
+                raise ValueError("%s: the path 'skip' is defined at subgrid_size 1 only" % what)
+            self.skip_fields(reflector[0], reflector[1], sources=union, veln=veln, velpn=velpn, vel_map=vel_map,
+                             stif_den=stif_den)
+            slots = self.skip_slots
+            txs = [slots[tx_path][i] for i in tx]
+            rxs = [slots[rx_path][i] for i in rx]
+        else:
+            res = self._fields(veln, velpn, vel_map, stif_den, subgrid_size, union, [0], copy_out=False)
+            txs, rxs = [res[i][1] for i in tx], [res[i][1] for i in rx]
+        return txs, rxs
+
     def tfm(self, fmc, fs, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1, veln=None,
             velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct", reflector=None):
         """Total-focusing-method image of full-matrix-capture data fmc[(a, b, t)] with the
@@ -649,36 +683,47 @@ class ALI_FMM:
 
         One GPU (device 0) only: every GPU would need every field, and sharding the pixels over
         GPUs is not implemented."""
-        veln = self.veln if veln is None else veln
-        velpn = self.velpn if velpn is None else velpn
-        vel_map = self.vel_map if vel_map is None else vel_map
-        if vel_map is None:
-            vel_map = np.ones(np.shape(veln))
-        stif_den = self.stif_den if stif_den is None else stif_den
-        tx = list(range(self.nsrc)) if tx is None else [int(i) for i in tx]
-        rx = list(range(self.nsrc)) if rx is None else [int(i) for i in rx]
-        for i in tx + rx:
-            if not 0 <= i < self.nsrc:
-                raise IndexError("tfm: element %d of %d" % (i, self.nsrc))
-        for p in (tx_path, rx_path):
-            if p not in ("direct", "skip"):
-                raise ValueError("tfm: path %r is neither 'direct' nor 'skip'" % (p,))
-        union = sorted(set(tx) | set(rx))
-        if "skip" in (tx_path, rx_path):
-            if reflector is None:
-                raise ValueError("tfm: the path 'skip' needs reflector=(iz, ix)")
-            if int(subgrid_size) != 1:
-                raise ValueError("tfm: the path 'skip' is defined at subgrid_size 1 only")
-            self.skip_fields(reflector[0], reflector[1], sources=union, veln=veln, velpn=velpn, vel_map=vel_map,
-                             stif_den=stif_den)
-            slots = self.skip_slots
-            txs = [slots[tx_path][i] for i in tx]
-            rxs = [slots[rx_path][i] for i in rx]
-        else:
-            res = self._fields(veln, velpn, vel_map, stif_den, subgrid_size, union, [0], copy_out=False)
-            txs, rxs = [res[i][1] for i in tx], [res[i][1] for i in rx]
+        txs, rxs = self._pair_slots("tfm", tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path, rx_path,
+                                    reflector)
         return self._ctx(0).tfm(txs, rxs, fmc, fs, t0=t0, weights=weights, window=window, step=step,
                                 subgrid=int(subgrid_size))
+
+    def simulate_fmc(self, refl, fs, nt, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1,
+                     veln=None, velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct",
+                     reflector=None, pulse=None):
+        """Full-matrix-capture data that the reflectivity map refl predicts under the first-arrival
+        delay laws: the transpose of tfm(), term by term (no counterpart in the reference).  Pixel p
+        adds w_ab refl(p) to the trace of every pair (a, b) at the time T_a(p) + T_b(p), split
+        linearly over the two samples around it.
+
+        refl: (niz, nix) real or complex on the pixel window, every value finite; a side-drilled
+        hole is one pixel, a crack a line of pixels; zero pixels cost nothing.  nt samples per trace
+        at fs [Hz] from t0 [s].  tx, rx, weights, window, step, subgrid_size, the model arguments,
+        tx_path, rx_path and reflector: as in tfm(), with the same field computation (the fields
+        stay on the device, _alifmm.Context.tfm_model reads them there) and the same checks.
+        pulse: 1-D real or complex wavelet applied on the host after the call,
+        out[..., k] = sum_j pulse[j] d[..., k - j], truncated to nt (numpy's FFT in float64; the
+        device does not convolve).
+        Returns float64 (len(tx), len(rx), nt), or complex128 when refl or pulse is complex.  The
+        order of the device's sums is not fixed: two calls agree to rounding, not to the bit.
+
+        One GPU (device 0) only, as tfm()."""
+        txs, rxs = self._pair_slots("simulate_fmc", tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path,
+                                    rx_path, reflector)
+        d = self._ctx(0).tfm_model(txs, rxs, refl, fs, nt, t0=t0, weights=weights, window=window, step=step,
+                                   subgrid=int(subgrid_size))
+        if pulse is None:
+            return d
+        pulse = np.asarray(pulse)
+        if pulse.ndim != 1 or pulse.size < 1:
+            raise ValueError("simulate_fmc: pulse must be a non-empty 1-D array")
+        n = d.shape[-1] + pulse.size - 1
+        cplx = np.iscomplexobj(d) or np.iscomplexobj(pulse)
+        if cplx:
+            out = np.fft.ifft(np.fft.fft(d, n, axis=-1) * np.fft.fft(pulse.astype(np.complex128), n), axis=-1)
+        else:
+            out = np.fft.irfft(np.fft.rfft(d, n, axis=-1) * np.fft.rfft(pulse.astype(np.float64), n), n, axis=-1)
+        return np.ascontiguousarray(out[..., :d.shape[-1]])
 
     def plot_phase(self, material_index=1):
         import matplotlib.pyplot as plt

@@ -85,6 +85,7 @@ def _load():
             "alifmm_init_profile": (_i, [_p, _i, _p]),
             "alifmm_put_field": (_i, [_p, _i, _i, _p]),
             "alifmm_tfm": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
+            "alifmm_tfm_model": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
             "alifmm_ray_sens": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p]),
             "alifmm_sens_op_build": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
             "alifmm_sens_op_apply": (_i, [_p, _i, _p, _p]),
@@ -370,6 +371,42 @@ class Context:
                                    fmc.shape[2], nc, float(t0), float(fs), _ptr(w), iz0, ix0, niz, nix, step,
                                    _ptr(img)), "tfm")
         return img.view(np.complex128)[..., 0] if cplx else img[..., 0]
+
+    def tfm_model(self, tx_slots, rx_slots, refl, fs, nt, t0=0.0, weights=None, window=None, step=1, subgrid=1):
+        """Full-matrix-capture data a reflectivity map predicts under the delay laws of resident
+        fields (alifmm_tfm_model), the exact transpose of tfm(): pixel p adds w_ab refl(p), split
+        linearly over the two samples around T_a(p) + T_b(p), to the trace of every pair (a, b); all
+        in float64.  The fields stay on the device and the data come back.  The order of the sums
+        is not fixed: two calls agree to rounding, not to the bit.
+
+        tx_slots, rx_slots, fs, t0, weights, window, step, subgrid: as in tfm().  refl: (niz, nix)
+        real or complex on the pixel window, every value finite; zero pixels cost nothing.  nt:
+        samples per trace.  Returns float64 (ntx, nrx, nt), or complex128 when refl is complex."""
+        tx, rx = _ci32(np.atleast_1d(tx_slots)), _ci32(np.atleast_1d(rx_slots))
+        refl = np.asarray(refl)
+        cplx = np.iscomplexobj(refl)
+        step = int(step)
+        if window is None:
+            if step < 1:
+                raise AlifmmError("tfm_model: step %d" % step)
+            fz, fx = self.field_shape(subgrid)
+            window = (0, 0, (fz - 1) // step + 1, (fx - 1) // step + 1)
+        iz0, ix0, niz, nix = (int(v) for v in window)
+        if refl.ndim != 2 or refl.shape != (max(niz, 0), max(nix, 0)):
+            raise ValueError("refl must have the window's shape (%d, %d), not %s" % (niz, nix, refl.shape))
+        x = np.ascontiguousarray(refl, dtype=np.complex128 if cplx else np.float64)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != (len(tx), len(rx)):
+                raise ValueError("weights must have shape (ntx, nrx)")
+        nc = 2 if cplx else 1
+        nt = int(nt)
+        out = np.empty((len(tx), len(rx), max(nt, 0), nc))
+        self._chk(lib().alifmm_tfm_model(self._h, int(subgrid), len(tx), _ptr(tx), len(rx), _ptr(rx), _ptr(x), nc, nt,
+                                         float(t0), float(fs), _ptr(w), iz0, ix0, niz, nix, step, _ptr(out)),
+                  "tfm_model")
+        return out.view(np.complex128)[..., 0] if cplx else out[..., 0]
 
     def copy_fields(self, first_slot, n, subgrid, out=None, dst_kind=0):
         """Resident fields of slots first_slot .. first_slot+n-1 as one (n, fnz, fnx) host array

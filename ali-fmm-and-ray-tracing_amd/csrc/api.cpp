@@ -280,6 +280,9 @@ int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   free_ray_bufs(ctx);
   dfree(ctx->tfm.fmc); dfree(ctx->tfm.w); dfree(ctx->tfm.tab); dfree(ctx->tfm.img);
   ctx->tfm = alifmm_ctx::TfmBufs();
+  dfree(ctx->tfm_model.pix); dfree(ctx->tfm_model.refl); dfree(ctx->tfm_model.w); dfree(ctx->tfm_model.tab);
+  dfree(ctx->tfm_model.out);
+  ctx->tfm_model = alifmm_ctx::TfmModelBufs();
   dfree(ctx->skip.tab); dfree(ctx->skip.wiz); dfree(ctx->skip.wix); dfree(ctx->skip.row); dfree(ctx->skip.hit);
   dfree(ctx->skip.W); dfree(ctx->skip.pick);
   ctx->skip = alifmm_ctx::SkipBufs();
@@ -331,6 +334,12 @@ int alifmm_set_option(alifmm_ctx* ctx, const char* name, double value) {
   else if (!strcmp(name, "stripe_log") && (value == 0 || (value >= 3 && value <= 12))) ctx->stripe_log = (int)value;
   else if (!strcmp(name, "xcd_local")) ctx->xcd_local = value != 0;
   else if (!strcmp(name, "tfm_chunk") && (value == 4 || value == 8 || value == 16 || value == 32)) ctx->tfm_chunk = (int)value;
+  else if (!strcmp(name, "tfm_model_tile") && value >= 0 && value <= 0x7fffffff && value == (int)value)
+    ctx->tfm_model_tile = (int)value;
+  else if (!strcmp(name, "tfm_model_slabs") && value >= 0 && value <= 64 && value == (int)value)
+    ctx->tfm_model_slabs = (int)value;
+  else if (!strcmp(name, "tfm_model_rx") && (value == 1 || value == 2 || value == 4)) ctx->tfm_model_rx = (int)value;
+  else if (!strcmp(name, "tfm_model_combine") && value >= 0 && value <= 64 && value == (int)value) ctx->tfm_model_combine = (int)value;
   else return fail(ctx, ALIFMM_E_ARG, "unknown option or bad value: %s=%g", name, value);
   return ALIFMM_OK;
 }
@@ -380,6 +389,17 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "tfm_upload_ms")) *value = ctx->t_tfm_upload;
   else if (!strcmp(name, "tfm_kernel_ms")) *value = ctx->t_tfm_kernel;
   else if (!strcmp(name, "tfm_chunk")) *value = ctx->tfm_chunk;
+  // last alifmm_tfm_model call (ms): the map's compaction and the host -> device copies (host clock);
+  // the zeroing of the output and the kernel (HIP events).  tile / slabs: the settings (0: automatic);
+  // *_used: what the last call ran with (kept apart, so that reading never pins an automatic choice)
+  else if (!strcmp(name, "tfm_model_upload_ms")) *value = ctx->t_tfm_model_upload;
+  else if (!strcmp(name, "tfm_model_kernel_ms")) *value = ctx->t_tfm_model_kernel;
+  else if (!strcmp(name, "tfm_model_tile")) *value = ctx->tfm_model_tile;
+  else if (!strcmp(name, "tfm_model_slabs")) *value = ctx->tfm_model_slabs;
+  else if (!strcmp(name, "tfm_model_rx")) *value = ctx->tfm_model_rx;
+  else if (!strcmp(name, "tfm_model_combine")) *value = ctx->tfm_model_combine;
+  else if (!strcmp(name, "tfm_model_tile_used")) *value = ctx->tfm_model_tile_used;
+  else if (!strcmp(name, "tfm_model_slabs_used")) *value = ctx->tfm_model_slabs_used;
   // last alifmm_travel_seeded call: the seed pass (uploads and fmm_seed_kernel, HIP events, ms), the
   // seeds and the close cells handed over per field
   else if (!strcmp(name, "seed_ms")) *value = ctx->t_seed;
@@ -2288,6 +2308,113 @@ int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, in
   HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
   ctx->t_tfm_kernel = ms;
   HIPCHK(hipMemcpy(image, B.img, nimg * sizeof(double), hipMemcpyDeviceToHost));
+  return ALIFMM_OK;
+}
+
+int alifmm_tfm_model(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+                     const double* refl, int ncomp, int nt, double t0, double fs, const float* pair_w, int iz0, int ix0,
+                     int niz, int nix, int step, double* fmc_out) {
+  if (!ctx) return ALIFMM_E_ARG;
+  if (!ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "tfm_model: no model");
+  if (!tx_slot || !rx_slot || !refl || !fmc_out) return fail(ctx, ALIFMM_E_ARG, "tfm_model: null pointer");
+  if (ntx < 1 || nrx < 1 || nt < 2) return fail(ctx, ALIFMM_E_ARG, "tfm_model: ntx %d, nrx %d, nt %d", ntx, nrx, nt);
+  if (ncomp != 1 && ncomp != 2) return fail(ctx, ALIFMM_E_ARG, "tfm_model: ncomp %d is not 1 or 2", ncomp);
+  if (!(std::isfinite(fs) && fs > 0) || !std::isfinite(t0)) return fail(ctx, ALIFMM_E_ARG, "tfm_model: fs %g, t0 %g", fs, t0);
+  if (step < 1 || niz < 1 || nix < 1) return fail(ctx, ALIFMM_E_ARG, "tfm_model: step %d, window %d x %d", step, niz, nix);
+  // the slots: resident fields of `subgrid`, one shape (as alifmm_tfm)
+  int fz = 0, fx = 0;
+  std::vector<const double*> tab((size_t)ntx + nrx);
+  for (int k = 0; k < ntx + nrx; k++) {
+    const int s = k < ntx ? tx_slot[k] : rx_slot[k - ntx];
+    if (s < 0 || s >= (int)ctx->fields.size() || !ctx->fields[s].d)
+      return fail(ctx, ALIFMM_E_ARG, "tfm_model: no field in slot %d", s);
+    const Field& f = ctx->fields[s];
+    if (f.sg != subgrid)
+      return fail(ctx, ALIFMM_E_ARG, "tfm_model: slot %d holds a subgrid-%d field, not %d", s, f.sg, subgrid);
+    if (k == 0) fz = f.nz, fx = f.nx;
+    if (f.nz != fz || f.nx != fx)
+      return fail(ctx, ALIFMM_E_ARG, "tfm_model: slot %d is %d x %d, slot %d is %d x %d", s, f.nz, f.nx, tx_slot[0], fz, fx);
+    tab[k] = f.d;
+  }
+  if (iz0 < 0 || ix0 < 0 || (int64_t)iz0 + (int64_t)step * (niz - 1) > fz - 1 ||
+      (int64_t)ix0 + (int64_t)step * (nix - 1) > fx - 1)
+    return fail(ctx, ALIFMM_E_ARG, "tfm_model: window (%d, %d) + %d x (%d, %d) outside the %d x %d field", iz0, ix0, step,
+                niz, nix, fz, fx);
+  const int rg = ctx->tfm_model_rx;
+  const int64_t ngroups = (int64_t)ntx * ((nrx + rg - 1) / rg);
+  if (ngroups > 0x7fffffffLL)
+    return fail(ctx, ALIFMM_E_ARG, "tfm_model: %d x %d pairs are more than one launch takes", ntx, nrx);
+  // the map: every value finite; the pixels that are not all zero, in raster order, as field offsets
+  // (a zero pixel never reaches the device)
+  const auto c0 = std::chrono::steady_clock::now();
+  std::vector<int64_t> pix;
+  std::vector<double> val;
+  for (int i = 0; i < niz; i++)
+    for (int j = 0; j < nix; j++) {
+      const double* x = refl + ((int64_t)i * nix + j) * ncomp;
+      bool any = false;
+      for (int c = 0; c < ncomp; c++) {
+        if (!std::isfinite(x[c]))
+          return fail(ctx, ALIFMM_E_ARG, "tfm_model: refl[%d][%d][%d] is %g", i, j, c, x[c]);
+        any |= x[c] != 0.0;
+      }
+      if (!any) continue;
+      pix.push_back(af::tfm_model_pixel_offset(iz0, ix0, step, fx, i, j));
+      for (int c = 0; c < ncomp; c++) val.push_back(x[c]);
+    }
+  const size_t npix = pix.size(), npair = (size_t)ntx * nrx, nout = npair * (size_t)nt * ncomp;
+  // the knobs in force
+  const int tile = af::tfm_model_tile(ctx->tfm_model_tile, nt, ncomp, rg);
+  int64_t slabs = ctx->tfm_model_slabs;
+  if (slabs == 0) {  // two workgroups per CU where the pairs alone do not give them, a slab no shorter than a workgroup
+    slabs = (2 * (int64_t)std::max(ctx->n_cu, 1) + ngroups - 1) / ngroups;
+    slabs = std::min<int64_t>(slabs, ((int64_t)npix + 1023) / 1024);
+  }
+  slabs = std::max<int64_t>(1, std::min<int64_t>({slabs, 64, (int64_t)npix}));
+  ctx->tfm_model_tile_used = tile;
+  ctx->tfm_model_slabs_used = (int)slabs;
+  HIPCHK(hipSetDevice(ctx->device));
+  alifmm_ctx::TfmModelBufs& B = ctx->tfm_model;
+  HIPCHK(dgrow(&B.pix, &B.pix_n, npix));
+  HIPCHK(dgrow(&B.refl, &B.refl_n, val.size()));
+  if (pair_w) HIPCHK(dgrow(&B.w, &B.w_n, npair));
+  HIPCHK(dgrow(&B.tab, &B.tab_n, tab.size()));
+  HIPCHK(dgrow(&B.out, &B.out_n, nout));
+  if (npix) {
+    HIPCHK(hipMemcpy(B.pix, pix.data(), npix * sizeof(int64_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(B.refl, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  if (pair_w) HIPCHK(hipMemcpy(B.w, pair_w, npair * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(B.tab, tab.data(), tab.size() * sizeof(double*), hipMemcpyHostToDevice));
+  ctx->t_tfm_model_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+  af::TfmModelParams P;
+  P.tx = B.tab;
+  P.rx = B.tab + ntx;
+  P.pix = B.pix;
+  P.refl = B.refl;
+  P.pair_w = pair_w ? B.w : nullptr;
+  P.out = B.out;
+  P.t0 = t0;
+  P.fs = fs;
+  P.npix = (int64_t)npix;
+  P.ntx = ntx;
+  P.nrx = nrx;
+  P.nt = nt;
+  P.ncomp = ncomp;
+  P.rg = rg;
+  P.tile = tile;
+  P.slabs = (int)slabs;
+  P.combine = ctx->tfm_model_combine;
+  HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
+  // one slab stores every sample of its traces; several add into zeros; no pixel: all zeros
+  if (slabs > 1 || npix == 0) HIPCHK(hipMemsetAsync(B.out, 0, nout * sizeof(double), ctx->stream));
+  if (npix) HIPCHK(af_launch_tfm_model(&P, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+  ctx->t_tfm_model_kernel = ms;
+  HIPCHK(hipMemcpy(fmc_out, B.out, nout * sizeof(double), hipMemcpyDeviceToHost));
   return ALIFMM_OK;
 }
 

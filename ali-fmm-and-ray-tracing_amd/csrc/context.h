@@ -199,6 +199,21 @@ struct alifmm_ctx {
   } tfm;
   int tfm_chunk = af::kTfmChunk;  // receivers per register chunk of the TFM kernel (4, 8, 16, 32)
   double t_tfm_upload = 0, t_tfm_kernel = 0;  // last alifmm_tfm (ms)
+  // alifmm_tfm_model: grow-only device buffers (the non-zero pixels' field offsets and
+  // reflectivities, pair weights, slot pointer table, modelled data), freed with the context
+  struct TfmModelBufs {
+    int64_t* pix = nullptr;
+    double* refl = nullptr;
+    float* w = nullptr;
+    const double** tab = nullptr;
+    double* out = nullptr;
+    size_t pix_n = 0, refl_n = 0, w_n = 0, tab_n = 0, out_n = 0;  // capacities in elements
+  } tfm_model;
+  int tfm_model_tile = 0, tfm_model_slabs = 0;            // the settings (0: automatic)
+  int tfm_model_rx = af::kTfmModelRx;                     // receivers per workgroup (1, 2, 4)
+  int tfm_model_combine = 12;  // a wave of at most this many runs of lanes sharing a sample sums each run before it adds
+  int tfm_model_tile_used = 0, tfm_model_slabs_used = 0;  // what the last alifmm_tfm_model ran with
+  double t_tfm_model_upload = 0, t_tfm_model_kernel = 0;  // last alifmm_tfm_model (ms)
   // alifmm_ray_sens: grow-only device buffers (a chunk of host points, the per-ray arrays of a
   // request, the three maps), freed with the context; the row arrays live for one call
   struct SensBufs {

@@ -4,6 +4,7 @@
 #include "fmm_shared.h"
 #include "solve_ops.h"  // the sums' geometry (kSolveMaxParts) of the resident sensitivity operator (sens_solve.hip)
 #include "tfm_term.h"  // af::TfmParams: the parameter block of the TFM kernel (tfm.hip) and of its host model
+#include "tfm_model_term.h"  // af::TfmModelParams: the same of the FMC modelling kernel (tfm_model.hip)
 
 namespace af {
 
@@ -245,6 +246,9 @@ hipError_t af_launch_tbp(const af::DevModel* M, int n, const double* x1, const d
                          const double* y2, double dnx, int sg, double* out, hipStream_t stream);
 // TFM delay-and-sum (tfm.hip); chunk = receivers per register chunk: 4, 8, 16 or 32
 hipError_t af_launch_tfm(const af::TfmParams* P, int chunk, hipStream_t stream);
+// FMC modelling, the transpose of the TFM sum (tfm_model.hip); P->tile from af::tfm_model_tile(),
+// P->slabs 1 .. 64 (> 1: P->out zeroed beforehand)
+hipError_t af_launch_tfm_model(const af::TfmModelParams* P, hipStream_t stream);
 // travel-time sensitivities along rays (ray_sens.hip): the count pass, then the fill pass
 hipError_t af_launch_sens_count(const af::SensParams* P, hipStream_t stream);
 hipError_t af_launch_sens_fill(const af::SensParams* P, hipStream_t stream);

@@ -334,6 +334,52 @@ int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, in
                const float* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
                int niz, int nix, int step, double* image);
 
+/* FMC modelling: the full-matrix-capture data a reflectivity map predicts under the delay laws of
+ * resident travel-time fields; the exact transpose of alifmm_tfm, term by term.  The fields stay on
+ * the device; the modelled data come back.
+ *   subgrid, tx_slot[ntx], rx_slot[nrx], t0, fs, pair_w, ncomp, iz0, ix0, niz, nix, step
+ *                      as in alifmm_tfm
+ *   refl               float64 [niz][nix][ncomp] on the pixel window (pixel (i, j) is node
+ *                      (iz0 + step i, ix0 + step j)); every value finite
+ *   fmc_out            float64 [ntx][nrx][nt][ncomp]
+ * For every pixel p whose components are not all zero and every pair (a, b), all in float64,
+ * operations in this order, no contraction:
+ *   1. w = pair_w ? (double)pair_w[a][b] : 1.0; if w == 0 there is no term
+ *   2. u = ((T_a(p) + T_b(p)) - t0) * fs
+ *   3. there is no term unless u >= 0 && u < nt - 1 (the test of alifmm_tfm step 3, made before
+ *      any conversion to an integer)
+ *   4. k = (int64)u, f = u - (double)k
+ *   5. per component c: g = w * refl[p][c], c1 = f * g, c0 = g - c1
+ *   6. the term adds c0 to fmc_out[a][b][k][c] and c1 to fmc_out[a][b][k+1][c]
+ * fmc_out[a][b][k][c] is the float64 sum of what the terms add to it, starting from +0.0.  The
+ * order of that sum is NOT fixed: the result is reproducible to rounding only, as the maps of
+ * alifmm_ray_sens are.  A sample that receives exactly one contribution has exactly that value, a
+ * sample that receives none is +0.0.  A pixel whose components are all +-0 contributes nothing and
+ * costs no field read (the map is compacted on the host, only its non-zero pixels are uploaded).
+ * The set of terms is exactly that of alifmm_tfm for the same slots, window, step, t0, fs, nt and
+ * weights, and the map is the transpose of that linear map: <tfm(d), x> = <d, model(x)> to
+ * rounding, component-wise.
+ * ALIFMM_E_ARG with a message, the context staying usable and nothing written to fmc_out: every
+ * condition of alifmm_tfm (refl / fmc_out in place of fmc / image), and a non-finite value in refl.
+ * The fields in the slots are not modified.  All offsets are 64-bit.  The non-zero pixels, the
+ * weights, the slot pointer table and the output live in grow-only device buffers of the context,
+ * freed with it.  alifmm_get_option: "tfm_model_upload_ms" (compaction and host -> device copies)
+ * and "tfm_model_kernel_ms" (zeroing and kernel) of the last call.  alifmm_set_option:
+ * "tfm_model_tile": samples of a trace a workgroup accumulates in LDS per pass (0, the default:
+ * the whole trace, at most what 128 KiB of LDS hold for two traces; larger values are cut to that);
+ * "tfm_model_slabs": slabs of the non-zero pixels per trace group, 0 (automatic) or 1 .. 64, cut to
+ * the number of non-zero pixels; with more than one the slabs' tiles are added into the zeroed
+ * output with float64 atomics; "tfm_model_rx": receivers of one transmitter per workgroup, 1, 2
+ * (default) or 4 (the LDS is shared by their traces, so the largest tile shrinks accordingly);
+ * "tfm_model_combine": 0 .. 64, default 12: a wave whose lanes fall into at most this many runs of
+ * neighbouring lanes that add to the same sample sums each run before its LDS atomics (0: never;
+ * another summation order, the same contract).  Read-only "tfm_model_tile_used" and
+ * "tfm_model_slabs_used": what the last call ran with (reading the settings back gives the
+ * settings, 0 for automatic).  One GPU. */
+int alifmm_tfm_model(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+                     const double* refl, int ncomp, int nt, double t0, double fs, const float* pair_w, int iz0, int ix0,
+                     int niz, int nix, int step, double* fmc_out);
+
 /* Travel-time sensitivities along rays: for every ray, the derivative of its time of flight in
  * every coarse cell it crosses (Fermat: to first order the path is fixed) — the rows of the
  * travel-time tomography Jacobian, and / or their weighted sums over the rays as three maps on the
