@@ -368,6 +368,7 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "stripe_log")) *value = ctx->stripe_log;
   else if (!strcmp(name, "xcd_local")) *value = ctx->xcd_local;
   else if (!strcmp(name, "last_k")) *value = ctx->last_k;
+  else if (!strcmp(name, "cap_scale")) *value = (double)ctx->cap_scale;  // read-only: x 4 per capacity retry
   else if (!strcmp(name, "n_cu")) *value = ctx->n_cu;
   else if (!strcmp(name, "vmax")) *value = ctx->vmax;  // model's fastest speed (set_model; the exact-walk stop)
   else if (!strcmp(name, "nmat")) *value = ctx->nmat;  // distinct material records (0: past the id table)

@@ -1237,6 +1237,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
     if (tid == 0) {
       sh->nF = max(0, nF - tk_);
       sh->nRb[par] = 0;  // the rim list of step + 2
+      // the two claim lists share capC evaluation slots: each may fit alone and their sum not, and
+      // the boundary claims past it were left out of this step (the clamp of nEb): a capacity error
+      atomicMax(&sh->err, (int)(unsigned)(sh->nE2 >> 32) > nEb ? 2 : 0);
     }
     if (prof) {
       ls[0] += hi - sh->nF;

@@ -161,6 +161,7 @@ int alifmm_travel_into(alifmm_ctx* ctx, int subgrid, int nsrc, const double* scx
  *    "xcd_local", alifmm_source_stats, alifmm_band_profile and alifmm_last_timing work as for
  *    alifmm_travel; init_ms is then the seed pass.  The fields are bit-identical for every member
  *    count and chunking, and a field does not depend on the other fields of its call.
+ *    alifmm_get_option "cap_scale" (read-only): 1 on a fresh context, x 4 per capacity retry so far.
  * 8. alifmm_get_option: "seed_ms" (uploads and the seed kernel of the last call), "seed_nodes" and
  *    "seed_close" (its seeds and close cells, set also when the call fails with ALIFMM_E_CAPACITY).
  * 9. A seed layer one node thick.  From a flat isotropic front given on one row, fouds18_A() finds

@@ -49,6 +49,25 @@ static inline void push_close(bstate_t *b, long idx) {
 static double g_cdelta_far = 0.0, g_r_far = 0.0;
 void oband_set_far(double cdelta_far, double r_far) { g_cdelta_far = cdelta_far; g_r_far = r_far; }
 
+/* optional record of the main grid's band run, for the list census of tests/long_cases.py: the
+   step at which each cell was accepted (acc[cell], the caller's fill elsewhere), and one entry per
+   close-list insertion and per evaluation: (cell, step, flag), flag bit 0: the cell was far (it
+   joins the close list), bit 1: update() returned -1 (fouds18_A() ran).  Step -1 holds the hand-over
+   (the initial close list; in a seeded run its evaluations).  Between oband_log_begin and
+   oband_log_end (the entry count, or -1 when cap was too small) on one thread. */
+static struct { int32_t *acc, *cell, *step; int8_t *flag; long cap, n; int on; } g_log;
+void oband_log_begin(int32_t *acc, int32_t *cell, int32_t *step, int8_t *flag, long cap) {
+    g_log.acc = acc; g_log.cell = cell; g_log.step = step; g_log.flag = flag; g_log.cap = cap; g_log.n = 0;
+    g_log.on = 1;
+}
+long oband_log_end(void) { g_log.on = 0; return g_log.n <= g_log.cap ? g_log.n : -1; }
+static inline void log_entry(long cell, long step, int flag) {
+    if (g_log.n < g_log.cap) {
+        g_log.cell[g_log.n] = (int32_t)cell; g_log.step[g_log.n] = (int32_t)step; g_log.flag[g_log.n] = (int8_t)flag;
+    }
+    g_log.n++;
+}
+
 /* one band run on a grid until the close list drains (main) or the window edge is hit (stages) */
 static long band_run(bstate_t *b, const mat_t *m, const loopcfg_t *c, double delta, int sweeps, double t0,
                      double delta_far, double tfar) {
@@ -56,6 +75,7 @@ static long band_run(bstate_t *b, const mat_t *m, const loopcfg_t *c, double del
     long nx = f->nnx, nz = f->nnz;
     long steps = 0;
     int finished = 0;
+    const int lg = g_log.on && !c->stage;
     while (b->nL > 0 && !finished) {
         double tmin = INFINITY;
         for (long e = 0; e < b->nL; e++) { double t = f->ttn[b->L[e]]; if (t < tmin) tmin = t; }
@@ -70,6 +90,7 @@ static long band_run(bstate_t *b, const mat_t *m, const loopcfg_t *c, double del
             if (f->ttn[idx] <= thr) {
                 f->nsts[idx] = S_KNOWN;
                 b->accstep[idx] = (int32_t)steps;
+                if (lg) g_log.acc[idx] = (int32_t)steps;
                 b->A[nA++] = (int32_t)idx;
             } else {
                 b->L2[nL2++] = (int32_t)idx;
@@ -109,6 +130,7 @@ static long band_run(bstate_t *b, const mat_t *m, const loopcfg_t *c, double del
                     if ((ix > 0 && b->accstep[r - 1] == steps) || (ix < nx - 1 && b->accstep[r + 1] == steps)) quirk = 1;
                 }
                 double v = oref_update_f(f, m, c->ph, iz, ix, c->dnx, quirk ? nx : nz, nx);
+                if (lg) log_entry(r, steps, (f->nsts[r] == S_FARC ? 1 : 0) | (v == -1.0 ? 2 : 0));
                 if (v == -1.0) v = oref_fouds18_f(f, m, c->av, iz, ix, c->dnx, c->dnz_fouds, nx, nz);
                 b->V[k] = v;
             }
@@ -247,6 +269,7 @@ int oband_travel(double scx, double scz, int nnz, int nnx, const double *veln, c
         fstate_free(&h, 0);
         fstate_free(&hprev_keep, 1);
     }
+    if (g_log.on) for (long e = 0; e < bm.nL; e++) log_entry(bm.L[e], -1, 1);
     steps[3] = band_run(&bm, base, &c, cdelta * dnx / vmax, sweeps, r0 * dnx / vmax, g_cdelta_far * dnx / vmax,
                         g_r_far > 0 && g_cdelta_far > 0 ? g_r_far * dnx / vmax : 0.0);
     bstate_free(&bm, 0);
@@ -254,6 +277,66 @@ int oband_travel(double scx, double scz, int nnz, int nnx, const double *veln, c
     free_base(&bb);
     if (steps_out) for (int i = 0; i < 4; i++) steps_out[i] = steps[i];
     (void)have_b;
+    return 0;
+}
+
+/* alifmm_travel_seeded (include/alifmm.h) as tests/seed_ref.py SeedRef.field states it, in C for the
+ * long lists of tests/long_cases.py: the seeds are known with their times; step -1 evaluates their far
+ * in-grid 4-neighbours in ascending cell order, Jacobi-style, and makes them close; the band runs
+ * from there (band_run, sweeps 1).  cdelta / cdelta_far: the widths in force. */
+static int cmp_i32(const void *a, const void *b) {
+    int32_t x = *(const int32_t *)a, y = *(const int32_t *)b;
+    return x < y ? -1 : x > y;
+}
+int oband_seeded(int nnz, int nnx, const double *veln, const int64_t *velpn, const double *vel_map,
+                 const int64_t *stif, const double *av_, const double *ph_, int ncol, double dnx, double dnz,
+                 long nseed, const int32_t *seed_cell, const double *seed_t, double cdelta, double vmax, double r0,
+                 double cdelta_far, double r_far, double *ttn, long *steps_out) {
+    base_t bb;
+    if (make_base(&bb, nnz, nnx, veln, velpn, vel_map, stif)) return -1;
+    table_t tav = {av_, ncol}, tph = {ph_, ncol};
+    loopcfg_t c = {&tav, &tph, dnx, dnz, 0, 0, 0, 0, 0, 0.0};
+    memset(ttn, 0, sizeof(double) * (size_t)nnz * nnx);
+    bstate_t b;
+    if (bstate_alloc(&b, nnz, nnx, ttn)) return -1;
+    fstate_t *f = &b.f;
+    long nx = nnx, nz = nnz;
+    for (long k = 0; k < nseed; k++) {
+        long s = seed_cell[k];
+        if (s < 0 || s >= nz * nx || f->nsts[s] == S_KNOWN) { bstate_free(&b, 0); free_base(&bb); return -2; }
+        f->ttn[s] = seed_t[k];
+        f->nsts[s] = S_KNOWN;
+    }
+    long nC = 0;
+    for (long k = 0; k < nseed; k++) {
+        long iz = seed_cell[k] / nx, ix = seed_cell[k] % nx;
+        long nb[4][2] = {{iz, ix - 1}, {iz, ix + 1}, {iz - 1, ix}, {iz + 1, ix}};
+        for (int q = 0; q < 4; q++) {
+            long z = nb[q][0], x = nb[q][1];
+            if (z < 0 || z >= nz || x < 0 || x >= nx) continue;
+            long r = z * nx + x;
+            if (f->nsts[r] == S_FAR) { f->nsts[r] = S_FARC; b.C[nC++] = (int32_t)r; }
+        }
+    }
+    qsort(b.C, (size_t)nC, sizeof(int32_t), cmp_i32);
+    for (long k = 0; k < nC; k++) {
+        long r = b.C[k], iz = r / nx, ix = r % nx;
+        double v = oref_update_f(f, &bb.m, c.ph, iz, ix, dnx, nz, nx);
+        if (g_log.on) log_entry(r, -1, 1 | (v == -1.0 ? 2 : 0));
+        if (v == -1.0) v = oref_fouds18_f(f, &bb.m, c.av, iz, ix, dnx, dnz, nx, nz);
+        b.V[k] = v;
+    }
+    for (long k = 0; k < nC; k++) {
+        long r = b.C[k];
+        f->ttn[r] = b.V[k];
+        f->nsts[r] = S_CLOSE;
+        b.L[b.nL++] = (int32_t)r;
+    }
+    long steps = band_run(&b, &bb.m, &c, cdelta * dnx / vmax, 1, r0 * dnx / vmax, cdelta_far * dnx / vmax,
+                          r_far > 0 && cdelta_far > 0 ? r_far * dnx / vmax : 0.0);
+    bstate_free(&b, 0);
+    free_base(&bb);
+    if (steps_out) *steps_out = steps;
     return 0;
 }
 

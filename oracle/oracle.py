@@ -69,6 +69,11 @@ def open_lib(path):
         L.oband_travel_finer.restype = _i
         L.oband_travel_finer.argtypes = [_d, _d, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _d, _d, _d, _d, _d, _d, _d, _d,
                                          _d, _d, _p, _p]
+        L.oband_seeded.restype = _i
+        L.oband_seeded.argtypes = [_i, _i, _p, _p, _p, _p, _p, _p, _i, _d, _d, _l, _p, _p, _d, _d, _d, _d, _d, _p, _p]
+        L.oband_log_begin.restype = None
+        L.oband_log_begin.argtypes = [_p, _p, _p, _p, _l]
+        L.oband_log_end.restype = _l
         _libs[path] = L
     return _libs[path]
 
@@ -260,6 +265,46 @@ def band_travel(scx, scz, veln, velpn, vel_map, stif_den, avlist2, phase_vel, vm
     if rc:
         raise RuntimeError("band model failed rc=%d" % rc)
     return out, steps
+
+
+BandLog = collections.namedtuple("BandLog", "acc cell step flag")
+
+
+def band_logged(run, ncells, lib=None, per_cell=8):
+    """run() (a band_travel or band_seeded call on the same `lib`) with the main grid's band run
+    recorded (oracle/band_model.c oband_log_begin) -> (run's result, BandLog): acc[cell] the step
+    at which the cell was accepted (-1: never, or known at the hand-over); one entry per close-list
+    insertion and evaluation: cell, step (-1: the hand-over) and flag (bit 0: the cell was far and
+    joins the close list, bit 1: update() returned -1 and fouds18_A() ran)."""
+    L = lib if lib is not None else globals()["lib"]()
+    cap = int(per_cell) * int(ncells) + 1024
+    acc = np.full(ncells, -1, dtype=np.int32)
+    cell, step, flag = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int8)
+    L.oband_log_begin(_ptr(acc), _ptr(cell), _ptr(step), _ptr(flag), cap)
+    try:
+        out = run()
+    finally:
+        n = L.oband_log_end()
+    if n < 0:
+        raise RuntimeError("band log: more than %d entries" % cap)
+    return out, BandLog(acc, cell[:n].copy(), step[:n].copy(), flag[:n].copy())
+
+
+def band_seeded(model, seed_cell, seed_t, dnx, dnz, vmax, cdelta, r0, cdelta_far=0.0, r_far=0.0, lib=None):
+    """alifmm_travel_seeded as tests/seed_ref.py states it, in C (oracle/band_model.c oband_seeded):
+    `model` from model(), seed_cell flat cell indices, the widths in force.  Returns (T, steps)."""
+    m = model
+    cells, t = np.ascontiguousarray(seed_cell, dtype=np.int32), _f64(seed_t)
+    assert cells.shape == t.shape and cells.ndim == 1
+    out = np.zeros((m.nnz, m.nnx))
+    steps = ctypes.c_long(0)
+    L = lib if lib is not None else globals()["lib"]()
+    rc = L.oband_seeded(m.nnz, m.nnx, _ptr(m.veln), _ptr(m.velpn), _ptr(m.vel_map), _ptr(m.stif), _ptr(m.av),
+                        _ptr(m.ph), m.ncol, float(dnx), float(dnz), len(cells), _ptr(cells), _ptr(t), float(cdelta),
+                        float(vmax), float(r0), float(cdelta_far), float(r_far), _ptr(out), ctypes.byref(steps))
+    if rc:
+        raise RuntimeError("band model (seeded) failed rc=%d" % rc)
+    return out, int(steps.value)
 
 
 FinerInfo = collections.namedtuple("FinerInfo", "steps pops close peak1 peak2 peakp")

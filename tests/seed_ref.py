@@ -75,3 +75,14 @@ class SeedRef:
                     L.append(r)
                 nsts[r] = 1
         return ttn.reshape(nz, nx)
+
+    def field_c(self, seed_iz, seed_ix, seed_t, vmax, cdelta, r0, cdelta_far=0.0, r_far=0.0, lib=None, log=False):
+        """field() by oracle/band_model.c oband_seeded: the same statement in C, for lists of thousands
+        of cells (tests/test_long_cases_ref.py holds the two bit-equal).  lib: a build from
+        oracle.open_lib (the correctly rounded one); log: also the run's oracle.BandLog."""
+        seeds = np.asarray(seed_iz, dtype=np.int64) * self.nx + np.asarray(seed_ix, dtype=np.int64)
+        run = lambda: O.band_seeded(self.m, seeds, seed_t, self.dnx, self.dnz, vmax, cdelta, r0, cdelta_far,  # noqa: E731
+                                    r_far, lib=lib)[0]
+        if not log:
+            return run()
+        return O.band_logged(run, self.nz * self.nx, lib=lib)
