@@ -628,7 +628,7 @@ class ALI_FMM:
         return out
 
     def _pair_slots(self, what, tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path, rx_path, reflector):
-        """The resident slots of the transmitters' and receivers' fields of tfm() and simulate_fmc()
+        """The resident slots of the transmitters' and receivers' fields of tfm(), simulate_fmc() and lsq_image()
         (`what` names the caller in messages): their argument checks, the fields of the union of
         the elements computed and left on the device, the skip_fields() route for "skip" paths."""
         veln = self.veln if veln is None else veln
@@ -687,6 +687,31 @@ class ALI_FMM:
                                     reflector)
         return self._ctx(0).tfm(txs, rxs, fmc, fs, t0=t0, weights=weights, window=window, step=step,
                                 subgrid=int(subgrid_size))
+
+    def lsq_image(self, fmc, fs, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1, veln=None,
+                  velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct", reflector=None, damp=0.0,
+                  smooth=0.0, max_iter=50, tol=1e-6):
+        """Least-squares image of full-matrix-capture data: the reflectivity map x on the pixel
+        window that minimises |simulate_fmc(x) - fmc|² + damp² |x|² + smooth² |D x|², by CGLS from
+        x = 0 (no counterpart in the reference).  A is simulate_fmc() without a pulse, Aᵀ is tfm()
+        on float64 data, D the first difference between 4-neighbour pixels.
+
+        fmc, fs, t0, tx, rx, weights, window, step, subgrid_size, the model arguments, tx_path,
+        rx_path and reflector: as in tfm(), with the same field computation and the same checks;
+        fmc is sent as float64 and every value must be finite.  The fields, the data and every
+        vector of the iteration stay on the device (_alifmm.Context.tfm_lsq); one image comes back.
+        damp is absolute, not relative to the operator: |A|_2 is of the order sqrt(len(tx) len(rx)),
+        and info["grad0"] = |Aᵀ fmc| gives the scale of the gradient the stop rule
+        |gradient| <= tol grad0 refers to.
+        Returns (image, info): image float64 (niz, nix) or complex128 for complex data, info =
+        dict(iterations, grad0, grad, rhs_norm, res_norm, reason).  The modelling sums have no
+        fixed order: two solves agree to rounding, not to the bit.
+
+        One GPU (device 0) only, as tfm()."""
+        txs, rxs = self._pair_slots("lsq_image", tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path, rx_path,
+                                    reflector)
+        return self._ctx(0).tfm_lsq(txs, rxs, fmc, fs, t0=t0, weights=weights, window=window, step=step,
+                                    subgrid=int(subgrid_size), damp=damp, smooth=smooth, max_iter=max_iter, tol=tol)
 
     def simulate_fmc(self, refl, fs, nt, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1,
                      veln=None, velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct",

@@ -86,6 +86,9 @@ def _load():
             "alifmm_put_field": (_i, [_p, _i, _i, _p]),
             "alifmm_tfm": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
             "alifmm_tfm_model": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
+            "alifmm_tfm_f64": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
+            "alifmm_tfm_lsq": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _d, _d, _i, _d,
+                                    _p, _p, _p]),
             "alifmm_ray_sens": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p]),
             "alifmm_sens_op_build": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
             "alifmm_sens_op_apply": (_i, [_p, _i, _p, _p]),
@@ -335,7 +338,31 @@ class Context:
             raise ValueError("field shape %s does not match subgrid %d" % (data.shape, subgrid))
         self._chk(lib().alifmm_put_field(self._h, int(slot), int(subgrid), _ptr(data)), "put_field")
 
-    def tfm(self, tx_slots, rx_slots, fmc, fs, t0=0.0, weights=None, window=None, step=1, subgrid=1):
+    def _tfm_args(self, what, tx_slots, rx_slots, fmc, weights, window, step, subgrid, f64):
+        """The arguments tfm() and tfm_lsq() share: (tx, rx, data, complex?, weights, window)."""
+        tx, rx = _ci32(np.atleast_1d(tx_slots)), _ci32(np.atleast_1d(rx_slots))
+        fmc = np.asarray(fmc)
+        if fmc.ndim != 3 or fmc.shape[:2] != (len(tx), len(rx)):
+            raise ValueError("fmc must have shape (ntx, nrx, nt) = (%d, %d, nt), not %s"
+                             % (len(tx), len(rx), fmc.shape))
+        cplx = np.iscomplexobj(fmc)
+        if f64:
+            data = np.ascontiguousarray(fmc, dtype=np.complex128 if cplx else np.float64)
+        else:
+            data = np.ascontiguousarray(fmc, dtype=np.complex64 if cplx else np.float32)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != fmc.shape[:2]:
+                raise ValueError("weights must have shape (ntx, nrx)")
+        if window is None:
+            if step < 1:
+                raise AlifmmError("%s: step %d" % (what, step))
+            fz, fx = self.field_shape(subgrid)
+            window = (0, 0, (fz - 1) // step + 1, (fx - 1) // step + 1)
+        return tx, rx, data, cplx, w, tuple(int(v) for v in window)
+
+    def tfm(self, tx_slots, rx_slots, fmc, fs, t0=0.0, weights=None, window=None, step=1, subgrid=1, precision="f32"):
         """Total-focusing-method image of full-matrix-capture data over resident fields
         (alifmm_tfm): I(p) = sum_ab w_ab s_ab(T_a(p) + T_b(p)), linear interpolation in time, all
         in float64; the fields stay on the device and one image comes back.
@@ -345,32 +372,57 @@ class Context:
         complex dtype; sent as float32 / interleaved float32), sample k taken at t0 + k / fs.
         weights: (ntx, nrx) or None.  window = (iz0, ix0, niz, nix) in pixels of `step` fine-grid
         nodes from node (iz0, ix0); None: the whole field at that step.
+        precision: "f32" (the default) sends the data as float32; "f64" sends them as float64
+        (alifmm_tfm_f64: the same sum in the same order, the samples read as they are; on data that
+        float32 represents exactly, the same bits).
         Returns float64 (niz, nix), or complex128 for complex data."""
-        tx, rx = _ci32(np.atleast_1d(tx_slots)), _ci32(np.atleast_1d(rx_slots))
-        fmc = np.asarray(fmc)
-        if fmc.ndim != 3 or fmc.shape[:2] != (len(tx), len(rx)):
-            raise ValueError("fmc must have shape (ntx, nrx, nt) = (%d, %d, nt), not %s"
-                             % (len(tx), len(rx), fmc.shape))
-        cplx = np.iscomplexobj(fmc)
-        data = np.ascontiguousarray(fmc, dtype=np.complex64 if cplx else np.float32)
-        w = None
-        if weights is not None:
-            w = np.ascontiguousarray(weights, dtype=np.float32)
-            if w.shape != fmc.shape[:2]:
-                raise ValueError("weights must have shape (ntx, nrx)")
+        if precision not in ("f32", "f64"):
+            raise ValueError("tfm: precision %r is neither 'f32' nor 'f64'" % (precision,))
         step = int(step)
-        if window is None:
-            if step < 1:
-                raise AlifmmError("tfm: step %d" % step)
-            fz, fx = self.field_shape(subgrid)
-            window = (0, 0, (fz - 1) // step + 1, (fx - 1) // step + 1)
-        iz0, ix0, niz, nix = (int(v) for v in window)
+        f64 = precision == "f64"
+        tx, rx, data, cplx, w, window = self._tfm_args("tfm", tx_slots, rx_slots, fmc, weights, window, step, subgrid, f64)
+        iz0, ix0, niz, nix = window
         nc = 2 if cplx else 1
         img = np.empty((max(niz, 0), max(nix, 0), nc))
-        self._chk(lib().alifmm_tfm(self._h, int(subgrid), len(tx), _ptr(tx), len(rx), _ptr(rx), _ptr(data),
-                                   fmc.shape[2], nc, float(t0), float(fs), _ptr(w), iz0, ix0, niz, nix, step,
-                                   _ptr(img)), "tfm")
+        call = lib().alifmm_tfm_f64 if f64 else lib().alifmm_tfm
+        self._chk(call(self._h, int(subgrid), len(tx), _ptr(tx), len(rx), _ptr(rx), _ptr(data), data.shape[2], nc,
+                       float(t0), float(fs), _ptr(w), iz0, ix0, niz, nix, step, _ptr(img)), "tfm")
         return img.view(np.complex128)[..., 0] if cplx else img[..., 0]
+
+    def tfm_lsq(self, tx_slots, rx_slots, fmc, fs, t0=0.0, weights=None, window=None, step=1, subgrid=1, damp=0.0,
+                smooth=0.0, max_iter=50, tol=1e-6, resid=False):
+        """Least-squares image of full-matrix-capture data over resident fields (alifmm_tfm_lsq):
+        CGLS from x = 0 on min |A x - fmc|² + damp² |x|² + smooth² |D x|², A being tfm_model() on
+        the dense window, Aᵀ tfm(precision="f64") and D the first difference between 4-neighbour
+        pixels.  The data, every vector and every scalar of the iteration stay on the device; one
+        image comes back.  A sums with atomics, so two solves agree to rounding, not to the bit,
+        and their iteration counts may differ by one.
+
+        tx_slots, rx_slots, fs, t0, weights, window, step, subgrid: as in tfm().  fmc: (ntx, nrx,
+        nt) real or complex, every value finite, sent as float64.  damp is absolute (|A|_2 is of the
+        order sqrt(ntx nrx)).
+        Returns (image, info), or (image, info, resid) with resid=True (the recurred residual, the
+        shape of fmc): image float64 (niz, nix) or complex128 for complex data; info =
+        dict(iterations, grad0 = |Aᵀ fmc|, grad, rhs_norm, res_norm, reason ("tol", "max_iter" or
+        "breakdown"))."""
+        step = int(step)
+        tx, rx, data, cplx, w, window = self._tfm_args("tfm_lsq", tx_slots, rx_slots, fmc, weights, window, step, subgrid,
+                                                       True)
+        iz0, ix0, niz, nix = window
+        nc = 2 if cplx else 1
+        img = np.zeros((max(niz, 0), max(nix, 0), nc))
+        res = np.zeros(data.shape + (nc,)) if resid else None
+        info = np.zeros(8)
+        self._chk(lib().alifmm_tfm_lsq(self._h, int(subgrid), len(tx), _ptr(tx), len(rx), _ptr(rx), _ptr(data),
+                                       data.shape[2], nc, float(t0), float(fs), _ptr(w), iz0, ix0, niz, nix, step,
+                                       float(damp), float(smooth), int(max_iter), float(tol), _ptr(img), _ptr(res),
+                                       _ptr(info)), "tfm_lsq")
+        out = {"iterations": int(info[0]), "grad0": info[1], "grad": info[2], "rhs_norm": info[3], "res_norm": info[4],
+               "reason": self.SOLVE_REASONS[int(info[5])]}
+        image = img.view(np.complex128)[..., 0] if cplx else img[..., 0]
+        if not resid:
+            return image, out
+        return image, out, (res.view(np.complex128)[..., 0] if cplx else res[..., 0])
 
     def tfm_model(self, tx_slots, rx_slots, refl, fs, nt, t0=0.0, weights=None, window=None, step=1, subgrid=1):
         """Full-matrix-capture data a reflectivity map predicts under the delay laws of resident

@@ -38,6 +38,11 @@ static void free_ray_bufs(alifmm_ctx* c) {
     if (p) (void)hipFree(p);
   b = alifmm_ctx::RayBufs();
 }
+static void free_tfm_lsq_bufs(alifmm_ctx* c) {
+  auto& b = c->tfm_lsq;
+  dfree(b.data); dfree(b.img); dfree(b.small); dfree(b.pix); dfree(b.w); dfree(b.tab);
+  b = alifmm_ctx::TfmLsqBufs();
+}
 // points kept by alifmm_find_rays(..., ALIFMM_KEEP_RAYS) for alifmm_take_rays
 static void release_kept_rays(alifmm_ctx* c) {
   for (auto& k : c->kept_dev) dfree(k.d);
@@ -278,8 +283,9 @@ int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   dfree(ctx->seed.from);
   ctx->seed = alifmm_ctx::SeedBufs();
   free_ray_bufs(ctx);
-  dfree(ctx->tfm.fmc); dfree(ctx->tfm.w); dfree(ctx->tfm.tab); dfree(ctx->tfm.img);
+  dfree(ctx->tfm.fmc); dfree(ctx->tfm.fmc64); dfree(ctx->tfm.w); dfree(ctx->tfm.tab); dfree(ctx->tfm.img);
   ctx->tfm = alifmm_ctx::TfmBufs();
+  free_tfm_lsq_bufs(ctx);
   dfree(ctx->tfm_model.pix); dfree(ctx->tfm_model.refl); dfree(ctx->tfm_model.w); dfree(ctx->tfm_model.tab);
   dfree(ctx->tfm_model.out);
   ctx->tfm_model = alifmm_ctx::TfmModelBufs();
@@ -401,6 +407,10 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "tfm_model_combine")) *value = ctx->tfm_model_combine;
   else if (!strcmp(name, "tfm_model_tile_used")) *value = ctx->tfm_model_tile_used;
   else if (!strcmp(name, "tfm_model_slabs_used")) *value = ctx->tfm_model_slabs_used;
+  // last alifmm_tfm_lsq call: host -> device copies (host clock), the whole solve (device), iterations
+  else if (!strcmp(name, "tfm_lsq_upload_ms")) *value = ctx->t_tfm_lsq_upload;
+  else if (!strcmp(name, "tfm_lsq_kernel_ms")) *value = ctx->t_tfm_lsq_kernel;
+  else if (!strcmp(name, "tfm_lsq_iters")) *value = ctx->tfm_lsq_iters;
   // last alifmm_travel_seeded call: the seed pass (uploads and fmm_seed_kernel, HIP events, ms), the
   // seeds and the close cells handed over per field
   else if (!strcmp(name, "seed_ms")) *value = ctx->t_seed;
@@ -2243,50 +2253,74 @@ int alifmm_put_field(alifmm_ctx* ctx, int slot, int subgrid, const double* data)
   return ALIFMM_OK;
 }
 
-int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
-               const float* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
-               int niz, int nix, int step, double* image) {
-  if (!ctx) return ALIFMM_E_ARG;
-  if (!ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "tfm: no model");
-  if (!tx_slot || !rx_slot || !fmc || !image) return fail(ctx, ALIFMM_E_ARG, "tfm: null pointer");
-  if (ntx < 1 || nrx < 1 || nt < 2) return fail(ctx, ALIFMM_E_ARG, "tfm: ntx %d, nrx %d, nt %d", ntx, nrx, nt);
-  if (ncomp != 1 && ncomp != 2) return fail(ctx, ALIFMM_E_ARG, "tfm: ncomp %d is not 1 or 2", ncomp);
-  if (!(std::isfinite(fs) && fs > 0) || !std::isfinite(t0)) return fail(ctx, ALIFMM_E_ARG, "tfm: fs %g, t0 %g", fs, t0);
-  if (step < 1 || niz < 1 || nix < 1) return fail(ctx, ALIFMM_E_ARG, "tfm: step %d, window %d x %d", step, niz, nix);
+// The argument checks of alifmm_tfm, shared with alifmm_tfm_f64 and alifmm_tfm_lsq (`what` names the
+// caller in messages); on success tab = the transmitters' fields, then the receivers', fx = their
+// row pitch
+static int tfm_check(alifmm_ctx* ctx, const char* what, int subgrid, int ntx, const int32_t* tx_slot, int nrx,
+                     const int32_t* rx_slot, const void* fmc, int nt, int ncomp, double t0, double fs, int iz0, int ix0,
+                     int niz, int nix, int step, const void* image, std::vector<const double*>& tab, int* fx_out) {
+  if (!ctx->have_model) return fail(ctx, ALIFMM_E_ARG, "%s: no model", what);
+  if (!tx_slot || !rx_slot || !fmc || !image) return fail(ctx, ALIFMM_E_ARG, "%s: null pointer", what);
+  if (ntx < 1 || nrx < 1 || nt < 2) return fail(ctx, ALIFMM_E_ARG, "%s: ntx %d, nrx %d, nt %d", what, ntx, nrx, nt);
+  if (ncomp != 1 && ncomp != 2) return fail(ctx, ALIFMM_E_ARG, "%s: ncomp %d is not 1 or 2", what, ncomp);
+  if (!(std::isfinite(fs) && fs > 0) || !std::isfinite(t0)) return fail(ctx, ALIFMM_E_ARG, "%s: fs %g, t0 %g", what, fs, t0);
+  if (step < 1 || niz < 1 || nix < 1) return fail(ctx, ALIFMM_E_ARG, "%s: step %d, window %d x %d", what, step, niz, nix);
   // the slots: resident fields of `subgrid`, one shape
   int fz = 0, fx = 0;
-  std::vector<const double*> tab((size_t)ntx + nrx);
+  tab.assign((size_t)ntx + nrx, nullptr);
   for (int k = 0; k < ntx + nrx; k++) {
     const int s = k < ntx ? tx_slot[k] : rx_slot[k - ntx];
     if (s < 0 || s >= (int)ctx->fields.size() || !ctx->fields[s].d)
-      return fail(ctx, ALIFMM_E_ARG, "tfm: no field in slot %d", s);
+      return fail(ctx, ALIFMM_E_ARG, "%s: no field in slot %d", what, s);
     const Field& f = ctx->fields[s];
-    if (f.sg != subgrid) return fail(ctx, ALIFMM_E_ARG, "tfm: slot %d holds a subgrid-%d field, not %d", s, f.sg, subgrid);
+    if (f.sg != subgrid) return fail(ctx, ALIFMM_E_ARG, "%s: slot %d holds a subgrid-%d field, not %d", what, s, f.sg, subgrid);
     if (k == 0) fz = f.nz, fx = f.nx;
     if (f.nz != fz || f.nx != fx)
-      return fail(ctx, ALIFMM_E_ARG, "tfm: slot %d is %d x %d, slot %d is %d x %d", s, f.nz, f.nx, tx_slot[0], fz, fx);
+      return fail(ctx, ALIFMM_E_ARG, "%s: slot %d is %d x %d, slot %d is %d x %d", what, s, f.nz, f.nx, tx_slot[0], fz, fx);
     tab[k] = f.d;
   }
   if (iz0 < 0 || ix0 < 0 || (int64_t)iz0 + (int64_t)step * (niz - 1) > fz - 1 ||
       (int64_t)ix0 + (int64_t)step * (nix - 1) > fx - 1)
-    return fail(ctx, ALIFMM_E_ARG, "tfm: window (%d, %d) + %d x (%d, %d) outside the %d x %d field", iz0, ix0, step, niz,
-                nix, fz, fx);
+    return fail(ctx, ALIFMM_E_ARG, "%s: window (%d, %d) + %d x (%d, %d) outside the %d x %d field", what, iz0, ix0, step,
+                niz, nix, fz, fx);
+  *fx_out = fx;
+  return ALIFMM_OK;
+}
+
+// alifmm_tfm (fmc float32) and alifmm_tfm_f64 (f64: fmc float64): the same call but for the data's type
+static int tfm_impl(alifmm_ctx* ctx, const char* what, bool f64, int subgrid, int ntx, const int32_t* tx_slot, int nrx,
+                    const int32_t* rx_slot, const void* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w,
+                    int iz0, int ix0, int niz, int nix, int step, double* image) {
+  if (!ctx) return ALIFMM_E_ARG;
+  std::vector<const double*> tab;
+  int fx = 0;
+  if (int rc = tfm_check(ctx, what, subgrid, ntx, tx_slot, nrx, rx_slot, fmc, nt, ncomp, t0, fs, iz0, ix0, niz, nix, step,
+                         image, tab, &fx))
+    return rc;
   const size_t npair = (size_t)ntx * nrx, ndata = npair * (size_t)nt * ncomp, nimg = (size_t)niz * nix * ncomp;
   HIPCHK(hipSetDevice(ctx->device));
   alifmm_ctx::TfmBufs& B = ctx->tfm;
-  HIPCHK(dgrow(&B.fmc, &B.fmc_n, ndata));
+  void* dfmc = nullptr;
+  if (f64) {
+    HIPCHK(dgrow(&B.fmc64, &B.fmc64_n, ndata));
+    dfmc = B.fmc64;
+  } else {
+    HIPCHK(dgrow(&B.fmc, &B.fmc_n, ndata));
+    dfmc = B.fmc;
+  }
   if (pair_w) HIPCHK(dgrow(&B.w, &B.w_n, npair));
   HIPCHK(dgrow(&B.tab, &B.tab_n, tab.size()));
   HIPCHK(dgrow(&B.img, &B.img_n, nimg));
   const auto c0 = std::chrono::steady_clock::now();
-  HIPCHK(hipMemcpy(B.fmc, fmc, ndata * sizeof(float), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dfmc, fmc, ndata * (f64 ? sizeof(double) : sizeof(float)), hipMemcpyHostToDevice));
   if (pair_w) HIPCHK(hipMemcpy(B.w, pair_w, npair * sizeof(float), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(B.tab, tab.data(), tab.size() * sizeof(double*), hipMemcpyHostToDevice));
   ctx->t_tfm_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
   af::TfmParams P;
   P.tx = B.tab;
   P.rx = B.tab + ntx;
-  P.fmc = B.fmc;
+  P.fmc = f64 ? nullptr : B.fmc;
+  P.fmc64 = f64 ? B.fmc64 : nullptr;
   P.pair_w = pair_w ? B.w : nullptr;
   P.image = B.img;
   P.t0 = t0;
@@ -2302,7 +2336,7 @@ int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, in
   P.nix = nix;
   P.step = step;
   HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-  HIPCHK(af_launch_tfm(&P, ctx->tfm_chunk, ctx->stream));
+  HIPCHK(f64 ? af_launch_tfm_f64(&P, ctx->tfm_chunk, ctx->stream) : af_launch_tfm(&P, ctx->tfm_chunk, ctx->stream));
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   float ms = 0;
@@ -2310,6 +2344,20 @@ int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, in
   ctx->t_tfm_kernel = ms;
   HIPCHK(hipMemcpy(image, B.img, nimg * sizeof(double), hipMemcpyDeviceToHost));
   return ALIFMM_OK;
+}
+
+int alifmm_tfm(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+               const float* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+               int niz, int nix, int step, double* image) {
+  return tfm_impl(ctx, "tfm", false, subgrid, ntx, tx_slot, nrx, rx_slot, fmc, nt, ncomp, t0, fs, pair_w, iz0, ix0, niz,
+                  nix, step, image);
+}
+
+int alifmm_tfm_f64(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+                   const double* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+                   int niz, int nix, int step, double* image) {
+  return tfm_impl(ctx, "tfm_f64", true, subgrid, ntx, tx_slot, nrx, rx_slot, fmc, nt, ncomp, t0, fs, pair_w, iz0, ix0, niz,
+                  nix, step, image);
 }
 
 int alifmm_tfm_model(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
@@ -2416,6 +2464,189 @@ int alifmm_tfm_model(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_sl
   HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
   ctx->t_tfm_model_kernel = ms;
   HIPCHK(hipMemcpy(fmc_out, B.out, nout * sizeof(double), hipMemcpyDeviceToHost));
+  return ALIFMM_OK;
+}
+
+// The device half of alifmm_tfm_lsq, after the checks: hipSuccess or the first error (the caller
+// frees the call's buffers on one).  out: iterations, reason, |d|², gamma_0, gamma, |r|²
+static hipError_t tfm_lsq_run(alifmm_ctx* ctx, const std::vector<const double*>& tab, int fx, int ntx, int nrx,
+                              const double* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0,
+                              int ix0, int niz, int nix, int step, double damp, double smooth, int max_iter, double tol,
+                              double* image, double* resid, double* out6) {
+#define LSQ(call)                          \
+  do {                                     \
+    hipError_t e_ = (call);                \
+    if (e_ != hipSuccess) return e_;       \
+  } while (0)
+  const size_t npix = (size_t)niz * nix, npair = (size_t)ntx * nrx;
+  const size_t nd = npair * (size_t)nt * ncomp, ni = npix * ncomp;
+  const int rg = ctx->tfm_model_rx;
+  const int64_t ngroups = (int64_t)ntx * ((nrx + rg - 1) / rg);
+  // the modelling kernel's knobs in force (alifmm_tfm_model), every pixel of the window counting
+  const int tile = af::tfm_model_tile(ctx->tfm_model_tile, nt, ncomp, rg);
+  int64_t slabs = ctx->tfm_model_slabs;
+  if (slabs == 0) {
+    slabs = (2 * (int64_t)std::max(ctx->n_cu, 1) + ngroups - 1) / ngroups;
+    slabs = std::min<int64_t>(slabs, ((int64_t)npix + 1023) / 1024);
+  }
+  slabs = std::max<int64_t>(1, std::min<int64_t>({slabs, 64, (int64_t)npix}));
+  ctx->tfm_model_tile_used = tile;
+  ctx->tfm_model_slabs_used = (int)slabs;
+  LSQ(hipSetDevice(ctx->device));
+  alifmm_ctx::TfmLsqBufs& B = ctx->tfm_lsq;
+  LSQ(dgrow(&B.data, &B.data_n, 2 * nd));
+  LSQ(dgrow(&B.img, &B.img_n, 4 * ni));
+  LSQ(dgrow(&B.small, &B.small_n, (size_t)af::kSolveMaxParts + af::kSolScalars));
+  LSQ(dgrow(&B.pix, &B.pix_n, npix));
+  if (pair_w) LSQ(dgrow(&B.w, &B.w_n, npair));
+  LSQ(dgrow(&B.tab, &B.tab_n, tab.size()));
+  af::SolveVecs V;
+  V.x = B.img;
+  V.p = B.img + ni;
+  V.s = B.img + 2 * ni;
+  V.t = B.img + 3 * ni;
+  V.xs = nullptr;
+  V.r = B.data;
+  V.q = B.data + nd;
+  V.parts = B.small;
+  V.scal = B.small + af::kSolveMaxParts;
+  V.damp2 = damp * damp;
+  V.smooth2 = smooth * smooth;
+  const auto c0 = std::chrono::steady_clock::now();
+  LSQ(hipMemcpy(V.r, fmc, nd * sizeof(double), hipMemcpyHostToDevice));
+  if (pair_w) LSQ(hipMemcpy(B.w, pair_w, npair * sizeof(float), hipMemcpyHostToDevice));
+  LSQ(hipMemcpy(B.tab, tab.data(), tab.size() * sizeof(double*), hipMemcpyHostToDevice));
+  ctx->t_tfm_lsq_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+  af::TfmLsqDims G;
+  G.niz = niz;
+  G.nix = nix;
+  G.nc = ncomp;
+  G.nimg = (int64_t)ni;
+  G.ndata = (int64_t)nd;
+  af::TfmParams T;  // t = Aᵀ r
+  T.tx = B.tab;
+  T.rx = B.tab + ntx;
+  T.fmc = nullptr;
+  T.fmc64 = V.r;
+  T.pair_w = pair_w ? B.w : nullptr;
+  T.image = V.t;
+  T.t0 = t0;
+  T.fs = fs;
+  T.ntx = ntx;
+  T.nrx = nrx;
+  T.nt = nt;
+  T.ncomp = ncomp;
+  T.fnx = fx;
+  T.iz0 = iz0;
+  T.ix0 = ix0;
+  T.niz = niz;
+  T.nix = nix;
+  T.step = step;
+  af::TfmModelParams M;  // q = A p
+  M.tx = B.tab;
+  M.rx = B.tab + ntx;
+  M.pix = B.pix;
+  M.refl = V.p;
+  M.pair_w = pair_w ? B.w : nullptr;
+  M.out = V.q;
+  M.t0 = t0;
+  M.fs = fs;
+  M.npix = (int64_t)npix;
+  M.ntx = ntx;
+  M.nrx = nrx;
+  M.nt = nt;
+  M.ncomp = ncomp;
+  M.rg = rg;
+  M.tile = tile;
+  M.slabs = (int)slabs;
+  M.combine = ctx->tfm_model_combine;
+  hipStream_t st = ctx->stream;
+  // one scalar of the device's (8 bytes) after the work queued so far
+  auto scalar = [&](int which, double* v) {
+    hipError_t e = hipMemcpyAsync(v, V.scal + which, 8, hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? hipStreamSynchronize(st) : e;
+  };
+  LSQ(hipEventRecord(ctx->ev[0], st));
+  LSQ(af_launch_tfm_lsq_pix(iz0, ix0, step, fx, niz, nix, B.pix, st));
+  LSQ(hipMemsetAsync(V.x, 0, 2 * ni * sizeof(double), st));  // x = p = 0
+  LSQ(hipMemsetAsync(V.scal, 0, af::kSolScalars * sizeof(double), st));
+  double rhs2 = 0, gamma0 = 0, gamma = 0, res2 = 0;
+  LSQ(af_launch_solve_norm(V.r, (long)nd, &V, st));
+  LSQ(scalar(af::kSolNorm, &rhs2));
+  // x = 0: s = Aᵀ d, p = s, gamma_0 = |s|²
+  LSQ(af_launch_tfm_f64(&T, ctx->tfm_chunk, st));
+  LSQ(af_launch_tfm_lsq_grad(&G, &V, 1, st));
+  LSQ(scalar(af::kSolReport, &gamma0));
+  gamma = gamma0;
+  int iters = 0, reason = 1;
+  if (gamma0 == 0.0) reason = 2;
+  else
+    for (int it = 1; it <= max_iter; it++) {
+      // several slabs add into q with atomics: zeroed every iteration
+      if (slabs > 1) LSQ(hipMemsetAsync(V.q, 0, nd * sizeof(double), st));
+      LSQ(af_launch_tfm_model(&M, st));
+      LSQ(af_launch_tfm_lsq_step(&G, &V, st));
+      LSQ(af_launch_tfm_f64(&T, ctx->tfm_chunk, st));
+      LSQ(af_launch_tfm_lsq_grad(&G, &V, 0, st));
+      double rep = 0;
+      LSQ(scalar(af::kSolReport, &rep));  // the one read of an iteration: the new gamma, -1: qq was 0
+      if (rep < 0) {
+        reason = 2;
+        break;
+      }
+      gamma = rep;
+      iters = it;
+      if (gamma <= tol * tol * gamma0) {
+        reason = 0;
+        break;
+      }
+    }
+  LSQ(af_launch_solve_norm(V.r, (long)nd, &V, st));
+  LSQ(scalar(af::kSolNorm, &res2));
+  LSQ(hipEventRecord(ctx->ev[1], st));
+  LSQ(hipStreamSynchronize(st));
+  float ms = 0;
+  LSQ(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+  ctx->t_tfm_lsq_kernel = ms;
+  ctx->tfm_lsq_iters = iters;
+  LSQ(hipMemcpy(image, V.x, ni * sizeof(double), hipMemcpyDeviceToHost));
+  if (resid) LSQ(hipMemcpy(resid, V.r, nd * sizeof(double), hipMemcpyDeviceToHost));
+  out6[0] = iters, out6[1] = reason, out6[2] = rhs2, out6[3] = gamma0, out6[4] = gamma, out6[5] = res2;
+  return hipSuccess;
+#undef LSQ
+}
+
+int alifmm_tfm_lsq(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+                   const double* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+                   int niz, int nix, int step, double damp, double smooth, int max_iter, double tol, double* image,
+                   double* resid, double* info8) {
+  if (!ctx) return ALIFMM_E_ARG;
+  std::vector<const double*> tab;
+  int fx = 0;
+  if (int rc = tfm_check(ctx, "tfm_lsq", subgrid, ntx, tx_slot, nrx, rx_slot, fmc, nt, ncomp, t0, fs, iz0, ix0, niz, nix,
+                         step, image, tab, &fx))
+    return rc;
+  if (!info8) return fail(ctx, ALIFMM_E_ARG, "tfm_lsq: info8 is NULL");
+  if (!(damp >= 0) || !std::isfinite(damp)) return fail(ctx, ALIFMM_E_ARG, "tfm_lsq: damp %g", damp);
+  if (!(smooth >= 0) || !std::isfinite(smooth)) return fail(ctx, ALIFMM_E_ARG, "tfm_lsq: smooth %g", smooth);
+  if (max_iter < 1) return fail(ctx, ALIFMM_E_ARG, "tfm_lsq: max_iter %d", max_iter);
+  if (!(tol >= 0) || !std::isfinite(tol)) return fail(ctx, ALIFMM_E_ARG, "tfm_lsq: tol %g", tol);
+  const int rg = ctx->tfm_model_rx;
+  if ((int64_t)ntx * ((nrx + rg - 1) / rg) > 0x7fffffffLL)
+    return fail(ctx, ALIFMM_E_ARG, "tfm_lsq: %d x %d pairs are more than one launch takes", ntx, nrx);
+  const size_t nd = (size_t)ntx * nrx * (size_t)nt * ncomp;
+  for (size_t k = 0; k < nd; k++)
+    if (!std::isfinite(fmc[k])) return fail(ctx, ALIFMM_E_ARG, "tfm_lsq: fmc[%zu] is not finite", k);
+  double o[6];
+  const hipError_t e = tfm_lsq_run(ctx, tab, fx, ntx, nrx, fmc, nt, ncomp, t0, fs, pair_w, iz0, ix0, niz, nix, step, damp,
+                                   smooth, max_iter, tol, image, resid, o);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(ctx->stream);
+    free_tfm_lsq_bufs(ctx);
+    return fail(ctx, ALIFMM_E_HIP, "tfm_lsq: %s", hipGetErrorString(e));
+  }
+  const double info[8] = {o[0], sqrt(o[3]), sqrt(o[4]), sqrt(o[2]), sqrt(o[5]), o[1], 0.0, 0.0};
+  memcpy(info8, info, sizeof info);
   return ALIFMM_OK;
 }
 

@@ -192,10 +192,11 @@ struct alifmm_ctx {
   // with the context
   struct TfmBufs {
     float* fmc = nullptr;
+    double* fmc64 = nullptr;  // alifmm_tfm_f64's data
     float* w = nullptr;
     const double** tab = nullptr;
     double* img = nullptr;
-    size_t fmc_n = 0, w_n = 0, tab_n = 0, img_n = 0;  // capacities in elements
+    size_t fmc_n = 0, fmc64_n = 0, w_n = 0, tab_n = 0, img_n = 0;  // capacities in elements
   } tfm;
   int tfm_chunk = af::kTfmChunk;  // receivers per register chunk of the TFM kernel (4, 8, 16, 32)
   double t_tfm_upload = 0, t_tfm_kernel = 0;  // last alifmm_tfm (ms)
@@ -214,6 +215,18 @@ struct alifmm_ctx {
   int tfm_model_combine = 12;  // a wave of at most this many runs of lanes sharing a sample sums each run before it adds
   int tfm_model_tile_used = 0, tfm_model_slabs_used = 0;  // what the last alifmm_tfm_model ran with
   double t_tfm_model_upload = 0, t_tfm_model_kernel = 0;  // last alifmm_tfm_model (ms)
+  // alifmm_tfm_lsq: grow-only device buffers (r and q: 2 x the data; x, p, s and t: 4 x the image;
+  // the window's pixel list, pair weights, slot pointer table, partial sums + scalars), freed with
+  // the context, or by a call whose allocation fails
+  struct TfmLsqBufs {
+    double *data = nullptr, *img = nullptr, *small = nullptr;
+    int64_t* pix = nullptr;
+    float* w = nullptr;
+    const double** tab = nullptr;
+    size_t data_n = 0, img_n = 0, small_n = 0, pix_n = 0, w_n = 0, tab_n = 0;  // capacities in elements
+  } tfm_lsq;
+  double t_tfm_lsq_upload = 0, t_tfm_lsq_kernel = 0;  // last alifmm_tfm_lsq (ms)
+  int tfm_lsq_iters = 0;
   // alifmm_ray_sens: grow-only device buffers (a chunk of host points, the per-ray arrays of a
   // request, the three maps), freed with the context; the row arrays live for one call
   struct SensBufs {

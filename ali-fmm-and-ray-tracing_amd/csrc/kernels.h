@@ -5,6 +5,7 @@
 #include "solve_ops.h"  // the sums' geometry (kSolveMaxParts) of the resident sensitivity operator (sens_solve.hip)
 #include "tfm_term.h"  // af::TfmParams: the parameter block of the TFM kernel (tfm.hip) and of its host model
 #include "tfm_model_term.h"  // af::TfmModelParams: the same of the FMC modelling kernel (tfm_model.hip)
+#include "tfm_solve_ops.h"  // af::TfmLsqDims: the vectors' shapes of the least-squares imaging solve (tfm_solve.hip)
 
 namespace af {
 
@@ -246,6 +247,8 @@ hipError_t af_launch_tbp(const af::DevModel* M, int n, const double* x1, const d
                          const double* y2, double dnx, int sg, double* out, hipStream_t stream);
 // TFM delay-and-sum (tfm.hip); chunk = receivers per register chunk: 4, 8, 16 or 32
 hipError_t af_launch_tfm(const af::TfmParams* P, int chunk, hipStream_t stream);
+// the same over the float64 samples P->fmc64
+hipError_t af_launch_tfm_f64(const af::TfmParams* P, int chunk, hipStream_t stream);
 // FMC modelling, the transpose of the TFM sum (tfm_model.hip); P->tile from af::tfm_model_tile(),
 // P->slabs 1 .. 64 (> 1: P->out zeroed beforehand)
 hipError_t af_launch_tfm_model(const af::TfmModelParams* P, hipStream_t stream);
@@ -266,4 +269,13 @@ hipError_t af_launch_solve_colprod(const af::SensOp* A, const double* y, double*
 hipError_t af_launch_solve_start(const af::SensOp* A, const af::SolveVecs* V, hipStream_t stream);
 hipError_t af_launch_solve_iter(const af::SensOp* A, const af::SolveVecs* V, hipStream_t stream);
 hipError_t af_launch_solve_norm(const double* v, long n, const af::SolveVecs* V, hipStream_t stream);
+// stage 2 of a two-stage sum over parts[nparts] and the scalar that follows from it: what 0 the norm,
+// 1 alpha, 2 the new gamma and beta, 3 the start (sens_solve.hip solve_scalar_kernel)
+hipError_t af_launch_solve_scalar(int what, const double* parts, int nparts, double* scal, hipStream_t stream);
+// least-squares imaging (tfm_solve.hip): the dense window's pixel list for af_launch_tfm_model; after
+// q = A p, alpha and x += alpha p, r -= alpha q; after t = Aᵀ r, s = t - R(x), gamma, beta (start:
+// gamma_0, beta 0, p zeroed by the caller) and p = s + beta p.  V->xs is not used.
+hipError_t af_launch_tfm_lsq_pix(int iz0, int ix0, int step, int fnx, int niz, int nix, int64_t* pix, hipStream_t stream);
+hipError_t af_launch_tfm_lsq_step(const af::TfmLsqDims* G, const af::SolveVecs* V, hipStream_t stream);
+hipError_t af_launch_tfm_lsq_grad(const af::TfmLsqDims* G, const af::SolveVecs* V, int start, hipStream_t stream);
 }

@@ -16,16 +16,9 @@
 
 #include "kernels.h"
 #include "solve_ops.h"
+#include "solve_sums.h"  // solve_block_sum, solve_part
 
 namespace af {
-
-// the workgroup's sum of a (solve_ops.h: wave tree, then the waves' sums); valid in thread 0
-AF_DEV double solve_block_sum(double a, double* w) {
-  a = solve_wave_tree(a, [](double v, int o) { return __shfl_xor(v, o); });
-  if ((threadIdx.x & (kSolveLanes - 1)) == 0) w[threadIdx.x / kSolveLanes] = a;
-  __syncthreads();
-  return solve_block_tree(w);
-}
 
 // ---- build ----
 
@@ -139,14 +132,6 @@ __global__ __launch_bounds__(kSolveBlock) void solve_colprod_kernel(SensOp A, co
 }
 
 // ---- CGLS ----
-
-// stage 1 of a two-stage sum over n elements (solve_ops.h solve_parts): parts[blockIdx.x]
-template <class Term>
-AF_DEV void solve_part(long n, double* parts, double* w, Term term) {
-  const double a = solve_block_sum(
-      solve_lane_sum(n, (int)(blockIdx.x * kSolveBlock + threadIdx.x), (int)(gridDim.x * kSolveBlock), term), w);
-  if (threadIdx.x == 0) parts[blockIdx.x] = a;
-}
 
 // |q|² = |A p|² + pᵀ(damp² p + smooth² DᵀD p): the cells' terms, then the rays'
 __global__ __launch_bounds__(kSolveBlock) void solve_qq_kernel(SensOp A, SolveVecs V) {
@@ -296,6 +281,17 @@ extern "C" hipError_t af_launch_solve_iter(const SensOp* A, const SolveVecs* V, 
   hipLaunchKernelGGL(solve_s_kernel, dim3(pc), b, 0, stream, *A, *V);
   hipLaunchKernelGGL(solve_scalar_kernel<2>, one, b, 0, stream, V->parts, pc, V->scal);
   hipLaunchKernelGGL(solve_p_kernel, solve_grid(A->ncell), b, 0, stream, *A, *V);
+  return hipGetLastError();
+}
+
+// stage 2 of a two-stage sum and its scalar (solve_scalar_kernel), for the CGLS of tfm_solve.hip
+extern "C" hipError_t af_launch_solve_scalar(int what, const double* parts, int nparts, double* scal, hipStream_t stream) {
+  const dim3 one(1), b(kSolveBlock);
+  if (what == 0) hipLaunchKernelGGL(solve_scalar_kernel<0>, one, b, 0, stream, parts, nparts, scal);
+  else if (what == 1) hipLaunchKernelGGL(solve_scalar_kernel<1>, one, b, 0, stream, parts, nparts, scal);
+  else if (what == 2) hipLaunchKernelGGL(solve_scalar_kernel<2>, one, b, 0, stream, parts, nparts, scal);
+  else if (what == 3) hipLaunchKernelGGL(solve_scalar_kernel<3>, one, b, 0, stream, parts, nparts, scal);
+  else return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

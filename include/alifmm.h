@@ -381,6 +381,62 @@ int alifmm_tfm_model(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_sl
                      const double* refl, int ncomp, int nt, double t0, double fs, const float* pair_w, int iz0, int ix0,
                      int niz, int nix, int step, double* fmc_out);
 
+/* alifmm_tfm on float64 data: the same signature and contract with fmc float64
+ * [ntx][nrx][nt][ncomp], the same term (steps 1 - 6, x0 and x1 read as they are), the same
+ * per-pixel summation order (a function of ntx, nrx and "tfm_chunk" only), the same errors.  Two
+ * consequences are part of the contract: on data whose every value float32 represents exactly the
+ * image has the bits of alifmm_tfm on those float32 data at the same "tfm_chunk"; and the image is
+ * bit-reproducible.  This is the A^T of an iterative method, whose residual d - A x is float64:
+ * alifmm_tfm would truncate it, and the pair would stop being A / A^T at about 6e-8.
+ * "tfm_upload_ms", "tfm_kernel_ms" and "tfm_chunk" are alifmm_tfm's (one option, one default). */
+int alifmm_tfm_f64(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+                   const double* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+                   int niz, int nix, int step, double* image);
+
+/* Least-squares imaging: min |A x - d|^2 + damp^2 |x|^2 + smooth^2 |D x|^2 by CGLS from x = 0, the
+ * imaging counterpart of alifmm_sens_op_solve.  The data, every vector and every scalar stay on the
+ * device; one image comes back.  The call is stateless like alifmm_tfm: the slots are resolved and
+ * validated at call time, there is no resident operator.
+ *   subgrid, tx_slot[ntx], rx_slot[nrx], nt, ncomp, t0, fs, pair_w, iz0, ix0, niz, nix, step
+ *                      as in alifmm_tfm
+ *   fmc                the data d, float64 [ntx][nrx][nt][ncomp], every value finite
+ *   image              x, float64 [niz][nix][ncomp]
+ *   resid (nullable)   the recurred residual r at the end, the shape of fmc
+ *   info8              iterations, sqrt(gamma_0), sqrt(gamma) at the end, |d|, the recurred |r| at the
+ *                      end, the stop's reason (0 tol, 1 max_iter, 2 breakdown), 0, 0
+ * A is the linear map of alifmm_tfm_model for these slots, window, step, t0, fs, nt and weights, on
+ * the dense window and component-wise; it is a real operator (a complex map is two real unknowns
+ * per pixel).  A zero pixel takes part as any other pixel: it adds zeros.  A^T is alifmm_tfm_f64.
+ * D is the first difference between 4-neighbour pixels of the window, per component:
+ * (D^T D p)[q] = sum over the neighbours q' of (p[q] - p[q']), upper, left, right, lower, in that
+ * order.  The iteration is alifmm_sens_op_solve's, word for word, with R(v) = damp^2 v +
+ * smooth^2 D^T D v:
+ *   r = d; s = A^T r; p = s; gamma_0 = gamma = |s|^2; gamma_0 == 0: stop (breakdown)
+ *   iteration it = 1, 2, ...:
+ *     q = A p; qq = |q|^2 + p . R(p); qq == 0: stop (breakdown; the iteration does not count)
+ *     alpha = gamma / qq; x += alpha p; r -= alpha q
+ *     s = A^T r - R(x); gamma' = |s|^2; beta = gamma' / gamma; p = s + beta p; gamma = gamma'
+ *     gamma <= tol^2 gamma_0: stop (tol); it == max_iter: stop (max_iter)
+ * The host reads 8 bytes per iteration for the stop rule.  Every dot product is a two-stage sum
+ * whose partial sums depend on the vector's length alone, and A^T has a fixed order; A sums with
+ * atomics in no fixed order (as alifmm_tfm_model does).  So a solve is reproducible to rounding
+ * only, NOT to the bit, and its iteration count may differ by one between two runs when gamma
+ * passes the threshold within rounding.  damp is absolute: |A|_2 is of the order sqrt(ntx nrx).
+ * ALIFMM_E_ARG with a message, the context staying usable and nothing written: every condition of
+ * alifmm_tfm; a non-finite value in fmc; damp or smooth negative or not finite; max_iter < 1; tol
+ * negative or not finite; image or info8 NULL.  A failed device allocation returns ALIFMM_E_HIP
+ * with the call's buffers freed.  The fields in the slots are not modified.  All offsets are 64-bit.
+ * The vectors (two of the data's size, four of the image's) and the pixel list live in grow-only
+ * device buffers of the context, freed with it.  alifmm_get_option: "tfm_lsq_upload_ms" (host ->
+ * device copies), "tfm_lsq_kernel_ms" (device time of the whole solve) and "tfm_lsq_iters" of the
+ * last call.  "tfm_chunk" and the "tfm_model_*" options apply as they do to the two kernels
+ * ("tfm_model_slabs" automatic counts every pixel of the window; with more than one slab q is
+ * zeroed every iteration).  One GPU. */
+int alifmm_tfm_lsq(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+                   const double* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+                   int niz, int nix, int step, double damp, double smooth, int max_iter, double tol, double* image,
+                   double* resid, double* info8);
+
 /* Travel-time sensitivities along rays: for every ray, the derivative of its time of flight in
  * every coarse cell it crosses (Fermat: to first order the path is fixed) — the rows of the
  * travel-time tomography Jacobian, and / or their weighted sums over the rays as three maps on the
