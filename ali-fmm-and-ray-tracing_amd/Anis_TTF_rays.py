@@ -688,6 +688,32 @@ class ALI_FMM:
         return self._ctx(0).tfm(txs, rxs, fmc, fs, t0=t0, weights=weights, window=window, step=step,
                                 subgrid=int(subgrid_size))
 
+    def tfm_coherence(self, fmc, fs, kind="pcf", power=1.0, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1,
+                      subgrid_size=1, veln=None, velpn=None, vel_map=None, stif_den=None, tx_path="direct",
+                      rx_path="direct", reflector=None):
+        """Coherence-weighted TFM image (no counterpart in the reference): tfm()'s image times
+        factor ** power, the factor in [0, 1] measuring per pixel how well the aperture's
+        contributions agree.  Grain noise adds up in the delay-and-sum almost as a flaw echo does,
+        but its contributions disagree in amplitude, sign and phase, so its factor is small.
+
+        kind: "cf" the coherence factor |sum t|² / (n sum |t|²); "scf" the sign coherence factor
+        1 - sqrt(1 - (sum sign Re t / n)²) and "pcf" (complex data only) the phase coherence factor
+        1 - sqrt(1 - |sum t / |t||² / n²) of Camacho, Parrilla and Fritsch (2009); n counts the
+        pairs whose delay falls inside the trace.  power: the exponent p (0 gives tfm()'s image).
+        fmc, fs, t0, tx, rx, weights, window, step, subgrid_size, the model arguments, tx_path,
+        rx_path and reflector: as in tfm(), with the same field computation and the same checks.
+        Both sums are made in one pass over the fields on the device (_alifmm.Context.tfm_coh); the
+        image and the factor come back and are multiplied here.
+        Returns (image * factor ** power, factor): the image float64 (niz, nix) or complex128 for
+        complex data, the factor float64 (niz, nix).
+
+        One GPU (device 0) only, as tfm()."""
+        txs, rxs = self._pair_slots("tfm_coherence", tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path,
+                                    rx_path, reflector)
+        image, factor = self._ctx(0).tfm_coh(txs, rxs, fmc, fs, kind=kind, t0=t0, weights=weights, window=window,
+                                             step=step, subgrid=int(subgrid_size))
+        return image * factor ** power, factor
+
     def lsq_image(self, fmc, fs, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1, veln=None,
                   velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct", reflector=None, damp=0.0,
                   smooth=0.0, max_iter=50, tol=1e-6):

@@ -87,6 +87,7 @@ def _load():
             "alifmm_tfm": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
             "alifmm_tfm_model": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
             "alifmm_tfm_f64": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _p]),
+            "alifmm_tfm_coh": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
             "alifmm_tfm_lsq": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _d, _d, _i, _d,
                                     _p, _p, _p]),
             "alifmm_ray_sens": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p]),
@@ -388,6 +389,37 @@ class Context:
         self._chk(call(self._h, int(subgrid), len(tx), _ptr(tx), len(rx), _ptr(rx), _ptr(data), data.shape[2], nc,
                        float(t0), float(fs), _ptr(w), iz0, ix0, niz, nix, step, _ptr(img)), "tfm")
         return img.view(np.complex128)[..., 0] if cplx else img[..., 0]
+
+    COHERENCE_KINDS = {"cf": 1, "scf": 2, "pcf": 3}
+
+    def tfm_coh(self, tx_slots, rx_slots, fmc, fs, kind="cf", t0=0.0, weights=None, window=None, step=1, subgrid=1,
+                sums=False):
+        """tfm() together with a per-pixel coherence factor in [0, 1] from a second sum over the
+        same terms, made in the same pass over the resident fields (alifmm_tfm_coh).
+
+        kind: "cf" the coherence factor |sum t|² / (n sum |t|²); "scf" the sign coherence factor
+        1 - sqrt(1 - (sum sign Re t / n)²); "pcf" the phase coherence factor
+        1 - sqrt(1 - |sum t / |t||² / n²), complex data only; n counts the terms in range.
+        tx_slots, rx_slots, fmc, fs, t0, weights, window, step, subgrid: as in tfm(), the data sent
+        as float32.
+        Returns (image, factor), or (image, factor, sums) with sums=True: image as tfm() returns it,
+        to the bit; factor float64 (niz, nix); sums float64 (niz, nix, 3), the raw sums (n, q, 0),
+        (n, b, 0) or (n, ph_re, ph_im) of the kind.  The weighted image is image * factor ** p."""
+        if kind not in self.COHERENCE_KINDS:
+            raise ValueError("tfm_coh: kind %r is none of 'cf', 'scf', 'pcf'" % (kind,))
+        step = int(step)
+        tx, rx, data, cplx, w, window = self._tfm_args("tfm_coh", tx_slots, rx_slots, fmc, weights, window, step, subgrid,
+                                                       False)
+        iz0, ix0, niz, nix = window
+        nc = 2 if cplx else 1
+        img = np.empty((max(niz, 0), max(nix, 0), nc))
+        fac = np.empty(img.shape[:2])
+        raw = np.empty(img.shape[:2] + (3,)) if sums else None
+        self._chk(lib().alifmm_tfm_coh(self._h, int(subgrid), len(tx), _ptr(tx), len(rx), _ptr(rx), _ptr(data),
+                                       data.shape[2], nc, float(t0), float(fs), _ptr(w), iz0, ix0, niz, nix, step,
+                                       self.COHERENCE_KINDS[kind], _ptr(img), _ptr(fac), _ptr(raw)), "tfm_coh")
+        image = img.view(np.complex128)[..., 0] if cplx else img[..., 0]
+        return (image, fac, raw) if sums else (image, fac)
 
     def tfm_lsq(self, tx_slots, rx_slots, fmc, fs, t0=0.0, weights=None, window=None, step=1, subgrid=1, damp=0.0,
                 smooth=0.0, max_iter=50, tol=1e-6, resid=False):

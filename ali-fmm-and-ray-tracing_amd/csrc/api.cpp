@@ -284,6 +284,7 @@ int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   ctx->seed = alifmm_ctx::SeedBufs();
   free_ray_bufs(ctx);
   dfree(ctx->tfm.fmc); dfree(ctx->tfm.fmc64); dfree(ctx->tfm.w); dfree(ctx->tfm.tab); dfree(ctx->tfm.img);
+  dfree(ctx->tfm.coh_f); dfree(ctx->tfm.coh_s);
   ctx->tfm = alifmm_ctx::TfmBufs();
   free_tfm_lsq_bufs(ctx);
   dfree(ctx->tfm_model.pix); dfree(ctx->tfm_model.refl); dfree(ctx->tfm_model.w); dfree(ctx->tfm_model.tab);
@@ -396,6 +397,9 @@ int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* value) {
   else if (!strcmp(name, "tfm_upload_ms")) *value = ctx->t_tfm_upload;
   else if (!strcmp(name, "tfm_kernel_ms")) *value = ctx->t_tfm_kernel;
   else if (!strcmp(name, "tfm_chunk")) *value = ctx->tfm_chunk;
+  // last alifmm_tfm_coh call (ms): the same two
+  else if (!strcmp(name, "tfm_coh_upload_ms")) *value = ctx->t_tfm_coh_upload;
+  else if (!strcmp(name, "tfm_coh_kernel_ms")) *value = ctx->t_tfm_coh_kernel;
   // last alifmm_tfm_model call (ms): the map's compaction and the host -> device copies (host clock);
   // the zeroing of the output and the kernel (HIP events).  tile / slabs: the settings (0: automatic);
   // *_used: what the last call ran with (kept apart, so that reading never pins an automatic choice)
@@ -2287,16 +2291,12 @@ static int tfm_check(alifmm_ctx* ctx, const char* what, int subgrid, int ntx, co
   return ALIFMM_OK;
 }
 
-// alifmm_tfm (fmc float32) and alifmm_tfm_f64 (f64: fmc float64): the same call but for the data's type
-static int tfm_impl(alifmm_ctx* ctx, const char* what, bool f64, int subgrid, int ntx, const int32_t* tx_slot, int nrx,
-                    const int32_t* rx_slot, const void* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w,
-                    int iz0, int ix0, int niz, int nix, int step, double* image) {
-  if (!ctx) return ALIFMM_E_ARG;
-  std::vector<const double*> tab;
-  int fx = 0;
-  if (int rc = tfm_check(ctx, what, subgrid, ntx, tx_slot, nrx, rx_slot, fmc, nt, ncomp, t0, fs, iz0, ix0, niz, nix, step,
-                         image, tab, &fx))
-    return rc;
+// What alifmm_tfm, alifmm_tfm_f64 and alifmm_tfm_coh share after the checks: the data, the weights
+// and the slot table `tab` go into the context's grow-only buffers (their copies' host time into
+// *t_upload), the image's buffer holds nimg values, and P is filled in full
+static int tfm_stage(alifmm_ctx* ctx, bool f64, const std::vector<const double*>& tab, int fx, int ntx, int nrx,
+                     const void* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+                     int niz, int nix, int step, af::TfmParams* Pout, double* t_upload) {
   const size_t npair = (size_t)ntx * nrx, ndata = npair * (size_t)nt * ncomp, nimg = (size_t)niz * nix * ncomp;
   HIPCHK(hipSetDevice(ctx->device));
   alifmm_ctx::TfmBufs& B = ctx->tfm;
@@ -2315,8 +2315,8 @@ static int tfm_impl(alifmm_ctx* ctx, const char* what, bool f64, int subgrid, in
   HIPCHK(hipMemcpy(dfmc, fmc, ndata * (f64 ? sizeof(double) : sizeof(float)), hipMemcpyHostToDevice));
   if (pair_w) HIPCHK(hipMemcpy(B.w, pair_w, npair * sizeof(float), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(B.tab, tab.data(), tab.size() * sizeof(double*), hipMemcpyHostToDevice));
-  ctx->t_tfm_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
-  af::TfmParams P;
+  *t_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - c0).count();
+  af::TfmParams& P = *Pout;
   P.tx = B.tab;
   P.rx = B.tab + ntx;
   P.fmc = f64 ? nullptr : B.fmc;
@@ -2335,14 +2335,40 @@ static int tfm_impl(alifmm_ctx* ctx, const char* what, bool f64, int subgrid, in
   P.niz = niz;
   P.nix = nix;
   P.step = step;
+  return ALIFMM_OK;
+}
+
+// `launch(stream)` between the context's two events, waited for; its device time into *t_kernel
+extern "C++" template <class F>
+static int tfm_timed(alifmm_ctx* ctx, F launch, double* t_kernel) {
   HIPCHK(hipEventRecord(ctx->ev[0], ctx->stream));
-  HIPCHK(f64 ? af_launch_tfm_f64(&P, ctx->tfm_chunk, ctx->stream) : af_launch_tfm(&P, ctx->tfm_chunk, ctx->stream));
+  HIPCHK(launch(ctx->stream));
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-  ctx->t_tfm_kernel = ms;
-  HIPCHK(hipMemcpy(image, B.img, nimg * sizeof(double), hipMemcpyDeviceToHost));
+  *t_kernel = ms;
+  return ALIFMM_OK;
+}
+
+// alifmm_tfm (fmc float32) and alifmm_tfm_f64 (f64: fmc float64): the same call but for the data's type
+static int tfm_impl(alifmm_ctx* ctx, const char* what, bool f64, int subgrid, int ntx, const int32_t* tx_slot, int nrx,
+                    const int32_t* rx_slot, const void* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w,
+                    int iz0, int ix0, int niz, int nix, int step, double* image) {
+  if (!ctx) return ALIFMM_E_ARG;
+  std::vector<const double*> tab;
+  int fx = 0;
+  if (int rc = tfm_check(ctx, what, subgrid, ntx, tx_slot, nrx, rx_slot, fmc, nt, ncomp, t0, fs, iz0, ix0, niz, nix, step,
+                         image, tab, &fx))
+    return rc;
+  af::TfmParams P;
+  if (int rc = tfm_stage(ctx, f64, tab, fx, ntx, nrx, fmc, nt, ncomp, t0, fs, pair_w, iz0, ix0, niz, nix, step, &P,
+                         &ctx->t_tfm_upload))
+    return rc;
+  const int chunk = ctx->tfm_chunk;
+  const auto launch = [&](hipStream_t st) { return f64 ? af_launch_tfm_f64(&P, chunk, st) : af_launch_tfm(&P, chunk, st); };
+  if (int rc = tfm_timed(ctx, launch, &ctx->t_tfm_kernel)) return rc;
+  HIPCHK(hipMemcpy(image, P.image, (size_t)niz * nix * ncomp * sizeof(double), hipMemcpyDeviceToHost));
   return ALIFMM_OK;
 }
 
@@ -2358,6 +2384,37 @@ int alifmm_tfm_f64(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot
                    int niz, int nix, int step, double* image) {
   return tfm_impl(ctx, "tfm_f64", true, subgrid, ntx, tx_slot, nrx, rx_slot, fmc, nt, ncomp, t0, fs, pair_w, iz0, ix0, niz,
                   nix, step, image);
+}
+
+int alifmm_tfm_coh(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+                   const float* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+                   int niz, int nix, int step, int kind, double* image, double* factor, double* sums) {
+  if (!ctx) return ALIFMM_E_ARG;
+  std::vector<const double*> tab;
+  int fx = 0;
+  if (int rc = tfm_check(ctx, "tfm_coh", subgrid, ntx, tx_slot, nrx, rx_slot, fmc, nt, ncomp, t0, fs, iz0, ix0, niz, nix,
+                         step, image, tab, &fx))
+    return rc;
+  if (!factor) return fail(ctx, ALIFMM_E_ARG, "tfm_coh: null pointer");
+  if (kind < 1 || kind > 3) return fail(ctx, ALIFMM_E_ARG, "tfm_coh: kind %d is not 1 (CF), 2 (SCF) or 3 (PCF)", kind);
+  if (kind == 3 && ncomp != 2) return fail(ctx, ALIFMM_E_ARG, "tfm_coh: kind 3 (PCF) needs ncomp 2, not %d", ncomp);
+  af::TfmCohParams Q;
+  if (int rc = tfm_stage(ctx, false, tab, fx, ntx, nrx, fmc, nt, ncomp, t0, fs, pair_w, iz0, ix0, niz, nix, step, &Q.T,
+                         &ctx->t_tfm_coh_upload))
+    return rc;
+  const size_t npix = (size_t)niz * nix;
+  alifmm_ctx::TfmBufs& B = ctx->tfm;
+  HIPCHK(dgrow(&B.coh_f, &B.coh_f_n, npix));
+  if (sums) HIPCHK(dgrow(&B.coh_s, &B.coh_s_n, 3 * npix));
+  Q.factor = B.coh_f;
+  Q.sums = sums ? B.coh_s : nullptr;
+  const int chunk = ctx->tfm_chunk;
+  const auto launch = [&](hipStream_t st) { return af_launch_tfm_coh(&Q, kind, chunk, st); };
+  if (int rc = tfm_timed(ctx, launch, &ctx->t_tfm_coh_kernel)) return rc;
+  HIPCHK(hipMemcpy(image, Q.T.image, npix * ncomp * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(factor, Q.factor, npix * sizeof(double), hipMemcpyDeviceToHost));
+  if (sums) HIPCHK(hipMemcpy(sums, Q.sums, 3 * npix * sizeof(double), hipMemcpyDeviceToHost));
+  return ALIFMM_OK;
 }
 
 int alifmm_tfm_model(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,

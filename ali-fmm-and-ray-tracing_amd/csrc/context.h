@@ -196,10 +196,12 @@ struct alifmm_ctx {
     float* w = nullptr;
     const double** tab = nullptr;
     double* img = nullptr;
-    size_t fmc_n = 0, fmc64_n = 0, w_n = 0, tab_n = 0, img_n = 0;  // capacities in elements
+    double *coh_f = nullptr, *coh_s = nullptr;  // alifmm_tfm_coh's factor and raw sums
+    size_t fmc_n = 0, fmc64_n = 0, w_n = 0, tab_n = 0, img_n = 0, coh_f_n = 0, coh_s_n = 0;  // capacities in elements
   } tfm;
   int tfm_chunk = af::kTfmChunk;  // receivers per register chunk of the TFM kernel (4, 8, 16, 32)
   double t_tfm_upload = 0, t_tfm_kernel = 0;  // last alifmm_tfm (ms)
+  double t_tfm_coh_upload = 0, t_tfm_coh_kernel = 0;  // last alifmm_tfm_coh (ms)
   // alifmm_tfm_model: grow-only device buffers (the non-zero pixels' field offsets and
   // reflectivities, pair weights, slot pointer table, modelled data), freed with the context
   struct TfmModelBufs {

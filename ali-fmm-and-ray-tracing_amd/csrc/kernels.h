@@ -4,6 +4,7 @@
 #include "fmm_shared.h"
 #include "solve_ops.h"  // the sums' geometry (kSolveMaxParts) of the resident sensitivity operator (sens_solve.hip)
 #include "tfm_term.h"  // af::TfmParams: the parameter block of the TFM kernel (tfm.hip) and of its host model
+#include "tfm_coh_term.h"  // af::TfmCohParams: the same of the coherence-weighted TFM kernel (tfm_coh.hip)
 #include "tfm_model_term.h"  // af::TfmModelParams: the same of the FMC modelling kernel (tfm_model.hip)
 #include "tfm_solve_ops.h"  // af::TfmLsqDims: the vectors' shapes of the least-squares imaging solve (tfm_solve.hip)
 
@@ -249,6 +250,9 @@ hipError_t af_launch_tbp(const af::DevModel* M, int n, const double* x1, const d
 hipError_t af_launch_tfm(const af::TfmParams* P, int chunk, hipStream_t stream);
 // the same over the float64 samples P->fmc64
 hipError_t af_launch_tfm_f64(const af::TfmParams* P, int chunk, hipStream_t stream);
+// coherence-weighted TFM (tfm_coh.hip): the image, the factor of `kind` (1 CF, 2 SCF, 3 PCF: ncomp 2
+// only) and, where Q->sums is set, its raw sums; chunk as in af_launch_tfm
+hipError_t af_launch_tfm_coh(const af::TfmCohParams* Q, int kind, int chunk, hipStream_t stream);
 // FMC modelling, the transpose of the TFM sum (tfm_model.hip); P->tile from af::tfm_model_tile(),
 // P->slabs 1 .. 64 (> 1: P->out zeroed beforehand)
 hipError_t af_launch_tfm_model(const af::TfmModelParams* P, hipStream_t stream);

@@ -393,6 +393,47 @@ int alifmm_tfm_f64(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot
                    const double* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
                    int niz, int nix, int step, double* image);
 
+/* Coherence-weighted TFM: alifmm_tfm's image together with a per-pixel factor in [0, 1] that says
+ * how well the aperture's contributions agree, from a second sum over the same terms made inside
+ * the same delay-and-sum.  The fields stay on the device; the image, the factor and, if asked for,
+ * the raw sums come back.  The exponent and the product image * factor^p are the caller's.
+ *   subgrid ... step   as in alifmm_tfm (fmc float32)
+ *   kind               1 the coherence factor (CF), 2 the sign coherence factor (SCF), 3 the phase
+ *                      (circular) coherence factor (PCF; ncomp 2 only)
+ *   image              float64 [niz][nix][ncomp]
+ *   factor             float64 [niz][nix]
+ *   sums (nullable)    float64 [niz][nix][3]: the raw sums of `kind`
+ * A counting term is a term (a, b) that passes steps 1 and 3 of alifmm_tfm (w != 0 and
+ * 0 <= u < nt - 1); t_c is its value of step 6 for component c.  A counting term whose value is 0
+ * counts.  Per pixel, all in float64, operations in the order written, no contraction, sqrt and /
+ * correctly rounded:
+ *   S_c = sum of t_c: image[p][c].  n = the number of counting terms.
+ *   kind 1: per term e = t_0 * t_0; if ncomp == 2: e = e + t_1 * t_1; q += e.
+ *           num = S_0 * S_0 (if ncomp == 2: + S_1 * S_1), den = n * q,
+ *           F = den > 0 ? num / den : 0.                               sums = (n, q, 0)
+ *   kind 2: per term b += (t_0 > 0) - (t_0 < 0) (component 0, the RF part).
+ *           m = b / n, y = 1 - m * m, F = n > 0 ? 1 - sqrt(y) : 0.     sums = (n, b, 0)
+ *   kind 3: per term e as in kind 1, g = sqrt(e); if g > 0: r = 1.0 / g, ph_c += t_c * r; where
+ *           g > 0 fails (g is 0 or NaN) the term adds nothing to ph and still counts in n.
+ *           num = ph_0 * ph_0 + ph_1 * ph_1, y = 1 - num / (n * n); if y < 0: y = 0;
+ *           F = n > 0 ? 1 - sqrt(y) : 0.                               sums = (n, ph_0, ph_1)
+ *   factor[p] = F.
+ * Every sum runs in alifmm_tfm's per-pixel order (a function of ntx, nrx and "tfm_chunk" only), so
+ * image has the bits of alifmm_tfm on the same call, and all three outputs are bit-reproducible and
+ * independent of the window, the step and the pixel's place in a tile.  n and b are exact integers,
+ * the same for every "tfm_chunk".  Non-finite data give non-finite values at the pixels they
+ * reach, as in alifmm_tfm.
+ * ALIFMM_E_ARG with a message, the context staying usable and nothing written: every condition of
+ * alifmm_tfm; kind outside 1 .. 3; kind 3 with ncomp != 2; image or factor NULL.
+ * The fields in the slots are not modified.  The data, the weights, the slot pointer table and the
+ * image use alifmm_tfm's device buffers; the factor and the sums live in grow-only device buffers of
+ * the context, freed with it.  alifmm_get_option: "tfm_coh_upload_ms" (host -> device copies) and
+ * "tfm_coh_kernel_ms" (the kernel) of the last call.  "tfm_chunk" applies as it does to alifmm_tfm.
+ * One GPU. */
+int alifmm_tfm_coh(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+                   const float* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+                   int niz, int nix, int step, int kind, double* image, double* factor, double* sums);
+
 /* Least-squares imaging: min |A x - d|^2 + damp^2 |x|^2 + smooth^2 |D x|^2 by CGLS from x = 0, the
  * imaging counterpart of alifmm_sens_op_solve.  The data, every vector and every scalar stay on the
  * device; one image comes back.  The call is stateless like alifmm_tfm: the slots are resolved and
