@@ -1,6 +1,7 @@
 // context.h — the host-side context behind include/alifmm.h (one GPU): resident model, work
-// arena, resident fields, ray buffers, pinned staging ring.  Shared by api.cpp (travel, copy,
-// rays) and comm.cpp (RCCL gather of resident fields).
+// arena, resident fields, the grow-only device buffers of every entry family (DevBuf), pinned
+// staging ring.  Shared by the host units (host_*.cpp, through host_internal.h) and comm.cpp
+// (RCCL gather of resident fields).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,10 +14,54 @@
 #include "../../include/alifmm.h"
 #include "kernels.h"
 
+template <class T>
+static inline hipError_t dalloc(T** p, size_t n) {
+  return hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
+}
+static inline void dfree(void* p) {
+  if (p) (void)hipFree(p);
+}
+// Owning device buffer of n elements (capacity, not bytes), grown on demand and never shrunk.
+// grow(need): nothing when the capacity suffices; otherwise the old buffer is freed first, then the
+// new one allocated (the peak is one buffer, not two), at least one element; after a failed
+// allocation the buffer is empty (capacity 0).  Move-only: a buffer is freed once, by release(),
+// by an assignment (`group = {}` releases every buffer of a struct of them) or with its owner.
+// Converts to its pointer, so launches and copies take it as they took the plain pointer.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p, n = o.n;
+      o.p = nullptr, o.n = 0;
+    }
+    return *this;
+  }
+  ~DevBuf() { release(); }
+  hipError_t grow(size_t need) {
+    if (p && n >= need) return hipSuccess;
+    release();
+    const hipError_t e = dalloc(&p, need);
+    if (e == hipSuccess) n = need;
+    return e;
+  }
+  void release() {
+    dfree(p);
+    p = nullptr;
+    n = 0;
+  }
+  operator T*() const { return p; }
+};
+
 struct Field {
-  double* d = nullptr;
+  DevBuf<double> d;  // the field + the K-member band kernel's edge buffers after it
   size_t bytes = 0;  // the field (fnz x fnx doubles)
-  size_t alloc = 0;  // allocated: the field + the K-member band kernel's edge buffers after it
   int sg = 0, nz = 0, nx = 0;
   int64_t steps[4] = {0, 0, 0, 0};
   int64_t sweeps = 0;
@@ -27,28 +72,28 @@ struct Field {
 struct Arena {  // per-chunk scratch, reused across calls
   int nsrc = 0;
   long cells = 0, scells = 0, capL = 0, capC = 0, capS = 0;
-  int* S = nullptr;  // row-major status, scells per source (subgrid > 1 only)
-  int* lists = nullptr;    // Lin | FS | A | L | C | Cp | D | Rx | Bl | Bp per source
-  double* dlists = nullptr;  // Lt | V | Dv per source
-  int K = 0;                 // K-member kernel: members the rim lists are sized for
+  DevBuf<int> S;          // row-major status, scells per source (subgrid > 1 only)
+  DevBuf<int> lists;      // Lin | FS | A | L | C | Cp | D | Rx | Bl | Bp per source
+  DevBuf<double> dlists;  // Lt | V | Dv per source
+  int K = 0;              // K-member kernel: members the rim lists are sized for
   long capR = 0, ecells = 0;
-  int* rimc = nullptr;       // K-member kernel: rim lists [src][K][2][capR]
-  double* rimt = nullptr;
-  af::KX* kx = nullptr;      // K-member kernel: exchange blocks
-  double* Tb = nullptr;      // band kernel: working fields + their edge buffers, tbc doubles per source
+  DevBuf<int> rimc;       // K-member kernel: rim lists [src][K][2][capR]
+  DevBuf<double> rimt;
+  DevBuf<af::KX> kx;      // K-member kernel: exchange blocks
+  DevBuf<double> Tb;      // band kernel: working fields + their edge buffers, tbc doubles per source
   long tbc = 0;
-  int* Sb = nullptr;         // band kernel: status arrays, sbc per source
+  DevBuf<int> Sb;         // band kernel: status arrays, sbc per source
   long sbc = 0;
-  double* Ts = nullptr;  // stage grids (travel_finer_grid), 2 per source
-  int* Ss = nullptr;
-  af::BandSrc* srcs = nullptr;
-  af::HandoverOut* ho = nullptr;
-  af::InitSig* sig = nullptr;  // a signature per slot of ho, allocated and zeroed with it
-  af::InitJob* jobs = nullptr;
-  int nho = 0;  // sources ho / sig / jobs are sized for (api.cpp ensure_handover): grown by a source-init
-                // launch alone, they outlive every regrowth of the rest (ensure_arena)
-  double* dscx = nullptr;
-  double* dscz = nullptr;
+  DevBuf<double> Ts;      // stage grids (travel_finer_grid), 2 per source
+  DevBuf<int> Ss;
+  DevBuf<af::BandSrc> srcs;
+  // the source-init hand-overs, a signature per slot (allocated and zeroed with it) and the jobs,
+  // sized together (host_travel.cpp ensure_handover): grown by a source-init launch alone, they
+  // outlive every regrowth of the rest (ensure_arena)
+  DevBuf<af::HandoverOut> ho;
+  DevBuf<af::InitSig> sig;
+  DevBuf<af::InitJob> jobs;
+  DevBuf<double> dscx, dscz;
 };
 
 
@@ -63,21 +108,20 @@ struct alifmm_ctx {
   bool have_model = false;
   int nz0 = 0, nx0 = 0, ncol = 0;
   double dnx = 0, dnz = 0, gox = 0, goz = 0, vmax = 0;
-  double* d_veln = nullptr;
-  double* d_vm = nullptr;
-  int* d_velpn = nullptr;
-  int* d_sidx = nullptr;
-  double* d_stab = nullptr;
+  struct ModelBufs {  // the resident model (DevModel points into these), released by set_model
+    DevBuf<double> veln, vm;
+    DevBuf<int> velpn, sidx;
+    DevBuf<double> stab;
+    DevBuf<int> mid;
+    DevBuf<unsigned char> mid8;   // the same ids as bytes when there are <= 256 materials
+    DevBuf<unsigned char> mid8b;  // ... in 8 x 16 bricks (DevModel::mid8b)
+    DevBuf<af::MatRec> mtab;
+    DevBuf<double> mslo;  // fouds18_A() slownesses per material (DevModel::mslo)
+    DevBuf<double> gtab, ptab;
+  } dm;
   int nstab = 0;
-  int* d_mid = nullptr;
-  unsigned char* d_mid8 = nullptr;  // the same ids as bytes when there are <= 256 materials
-  unsigned char* d_mid8b = nullptr; // ... in 8 x 16 bricks (DevModel::mid8b)
   int mid8b_pitch = 0;
-  af::MatRec* d_mtab = nullptr;
-  double* d_mslo = nullptr;  // fouds18_A() slownesses per material (DevModel::mslo)
   int nmat = 0;
-  double* d_gtab = nullptr;
-  double* d_ptab = nullptr;
   // options
   // band width (units of dnx / vmax): the caller's "cdelta" when set, else chosen from the model
   // (band_cdelta: 0.5, narrowed to 0.2 on models whose material changes from cell to cell)
@@ -93,15 +137,16 @@ struct alifmm_ctx {
   double cdelta_far = -1.0, r_far = 768.0;
   int far_sg = 1;  // largest subgrid the far band applies to (subgrid 9 weld rays: profiles/r5j)
   int exact_r = 20;
-  void* team = nullptr;  // api.cpp CopyTeam: host copy threads of the pinned staging ring
+  void* team = nullptr;  // host_fields.cpp CopyTeam: host copy threads of the pinned staging ring
   int exact_lds = 1;  // subgrid > 1: the LDS exact walk (fmm_exact_lds.hip) when it fits (0: fmm_exact.hip)
   int batch = 256;
   // subgrid-1 source init of a whole multi-launch travel call (one init launch for every chunk)
-  af::HandoverOut* ho_all = nullptr;
-  af::InitJob* jobs_all = nullptr;
-  af::InitSig* sig_all = nullptr;  // a signature per slot of ho_all, allocated and zeroed with it
-  int* reused_all = nullptr;       // per source of that launch: its walk was skipped
-  int n_all = 0;
+  struct InitAllBufs {
+    DevBuf<af::HandoverOut> ho;
+    DevBuf<af::InitJob> jobs;
+    DevBuf<af::InitSig> sig;  // a signature per slot of ho, allocated and zeroed with it
+    DevBuf<int> reused;       // per source of that launch: its walk was skipped
+  } all;
   // reuse of source-init hand-overs (fmm_shared.h InitSig): "init_reuse", "init_reused" (sources of
   // the last travel call whose walk was skipped)
   int init_reuse = 1;
@@ -115,15 +160,14 @@ struct alifmm_ctx {
   const af::HandoverOut* ho_last = nullptr;  // what alifmm_init_profile reads (last travel call)
   int n_ho_last = 0;
   // alifmm_travel_seeded: the seeded hand-overs (a buffer of their own: the InitSig signatures vouch
-  // for ho / ho_all only) and the call's geometry and times, grow-only, freed with the context
+  // for the arena's and all.ho only) and the call's geometry and times, grow-only, freed with the context
   struct SeedBufs {
-    af::HandoverOut* ho = nullptr;
-    int* cell = nullptr;    // seed cells, list order
-    int* close = nullptr;   // close cells, ascending
-    int* win = nullptr;     // [close][25] seed indices
-    double* t = nullptr;    // [nfield][nseed] host times
-    const double** from = nullptr;  // [nfield] source fields
-    size_t ho_n = 0, cell_n = 0, close_n = 0, win_n = 0, t_n = 0, from_n = 0;
+    DevBuf<af::HandoverOut> ho;
+    DevBuf<int> cell;            // seed cells, list order
+    DevBuf<int> close;           // close cells, ascending
+    DevBuf<int> win;             // [close][25] seed indices
+    DevBuf<double> t;            // [nfield][nseed] host times
+    DevBuf<const double*> from;  // [nfield] source fields
   } seed;
   double t_seed = 0;                   // last alifmm_travel_seeded: the seed pass (ms)
   long seed_nodes = 0, seed_close = 0; // its seeds and close cells
@@ -151,22 +195,20 @@ struct alifmm_ctx {
   };
   std::vector<KeptChunk> kept_dev;  // device-resident (one subgrid: the caller's order)
   int64_t kept_pts = 0;
-  // ray-tracer work buffers, kept across alifmm_find_rays calls (sized for the largest chunk seen)
+  // ray-tracer work buffers, kept across alifmm_find_rays calls (sized for the largest chunk seen:
+  // rx / ry hold its points, the others are per ray)
   struct RayBufs {
-    size_t pts = 0;  // capacity of rx / ry in doubles
-    int rays = 0;    // capacity of the per-ray arrays
-    double *rx = nullptr, *ry = nullptr, *t = nullptr;
-    int *len = nullptr, *flags = nullptr;
-    af::RayJob* jobs = nullptr;
-    long long* off = nullptr;
+    DevBuf<double> rx, ry, t;
+    DevBuf<int> len, flags;
+    DevBuf<af::RayJob> jobs;
+    DevBuf<long long> off;
   } rb;
   // alifmm_skip_pick / alifmm_skip_rays: grow-only device buffers (the distinct fields' pointer table,
   // the reflector nodes, W[field][node], the pairs' rows of W, the picks), freed with the context
   struct SkipBufs {
-    const double** tab = nullptr;
-    int *wiz = nullptr, *wix = nullptr, *row = nullptr, *hit = nullptr;  // row: [2][npairs]
-    double *W = nullptr, *pick = nullptr;
-    size_t tab_n = 0, wiz_n = 0, wix_n = 0, row_n = 0, hit_n = 0, W_n = 0, pick_n = 0;
+    DevBuf<const double*> tab;
+    DevBuf<int> wiz, wix, row, hit;  // row: [2][npairs]
+    DevBuf<double> W, pick;
   } skip;
   double t_skip_pick = 0, t_skip_join = 0;  // last skip_pick / skip_rays: the pick's kernels, the join kernel (ms)
   // pinned staging ring of alifmm_copy_fields (pageable destinations)
@@ -191,13 +233,12 @@ struct alifmm_ctx {
   // alifmm_tfm: grow-only device buffers (data, pair weights, slot pointer table, image), freed
   // with the context
   struct TfmBufs {
-    float* fmc = nullptr;
-    double* fmc64 = nullptr;  // alifmm_tfm_f64's data
-    float* w = nullptr;
-    const double** tab = nullptr;
-    double* img = nullptr;
-    double *coh_f = nullptr, *coh_s = nullptr;  // alifmm_tfm_coh's factor and raw sums
-    size_t fmc_n = 0, fmc64_n = 0, w_n = 0, tab_n = 0, img_n = 0, coh_f_n = 0, coh_s_n = 0;  // capacities in elements
+    DevBuf<float> fmc;
+    DevBuf<double> fmc64;  // alifmm_tfm_f64's data
+    DevBuf<float> w;
+    DevBuf<const double*> tab;
+    DevBuf<double> img;
+    DevBuf<double> coh_f, coh_s;  // alifmm_tfm_coh's factor and raw sums
   } tfm;
   int tfm_chunk = af::kTfmChunk;  // receivers per register chunk of the TFM kernel (4, 8, 16, 32)
   double t_tfm_upload = 0, t_tfm_kernel = 0;  // last alifmm_tfm (ms)
@@ -205,12 +246,11 @@ struct alifmm_ctx {
   // alifmm_tfm_model: grow-only device buffers (the non-zero pixels' field offsets and
   // reflectivities, pair weights, slot pointer table, modelled data), freed with the context
   struct TfmModelBufs {
-    int64_t* pix = nullptr;
-    double* refl = nullptr;
-    float* w = nullptr;
-    const double** tab = nullptr;
-    double* out = nullptr;
-    size_t pix_n = 0, refl_n = 0, w_n = 0, tab_n = 0, out_n = 0;  // capacities in elements
+    DevBuf<int64_t> pix;
+    DevBuf<double> refl;
+    DevBuf<float> w;
+    DevBuf<const double*> tab;
+    DevBuf<double> out;
   } tfm_model;
   int tfm_model_tile = 0, tfm_model_slabs = 0;            // the settings (0: automatic)
   int tfm_model_rx = af::kTfmModelRx;                     // receivers per workgroup (1, 2, 4)
@@ -221,22 +261,20 @@ struct alifmm_ctx {
   // the window's pixel list, pair weights, slot pointer table, partial sums + scalars), freed with
   // the context, or by a call whose allocation fails
   struct TfmLsqBufs {
-    double *data = nullptr, *img = nullptr, *small = nullptr;
-    int64_t* pix = nullptr;
-    float* w = nullptr;
-    const double** tab = nullptr;
-    size_t data_n = 0, img_n = 0, small_n = 0, pix_n = 0, w_n = 0, tab_n = 0;  // capacities in elements
+    DevBuf<double> data, img, small;
+    DevBuf<int64_t> pix;
+    DevBuf<float> w;
+    DevBuf<const double*> tab;
   } tfm_lsq;
   double t_tfm_lsq_upload = 0, t_tfm_lsq_kernel = 0;  // last alifmm_tfm_lsq (ms)
   int tfm_lsq_iters = 0;
   // alifmm_ray_sens: grow-only device buffers (a chunk of host points, the per-ray arrays of a
   // request, the three maps), freed with the context; the row arrays live for one call
   struct SensBufs {
-    double* xy = nullptr;
-    long long *off = nullptr, *cnt = nullptr, *row = nullptr;
-    int *len = nullptr, *flags = nullptr, *status = nullptr;
-    double *w = nullptr, *maps = nullptr;
-    size_t xy_n = 0, off_n = 0, cnt_n = 0, row_n = 0, len_n = 0, flags_n = 0, status_n = 0, w_n = 0, maps_n = 0;
+    DevBuf<double> xy;
+    DevBuf<long long> off, cnt, row;
+    DevBuf<int> len, flags, status;
+    DevBuf<double> w, maps;
   } sens;
   double t_sens_upload = 0, t_sens_kernel = 0;  // last alifmm_ray_sens (ms)
   int64_t sens_entries = 0;                     // its entries (row_ptr[nrays])
@@ -246,13 +284,12 @@ struct alifmm_ctx {
   struct SensOpBufs {
     bool have = false;
     af::SensOp A = {};
-    long long *row_ptr = nullptr, *col_ptr = nullptr;
-    int *col = nullptr, *row = nullptr, *cols = nullptr;
-    double *val = nullptr, *cval = nullptr, *cs = nullptr;
+    DevBuf<long long> row_ptr, col_ptr;
+    DevBuf<int> col, row, cols;
+    DevBuf<double> val, cval, cs;
   } op;
   struct SolveBufs {
-    double *cell = nullptr, *ray = nullptr, *small = nullptr;  // 5 x ncell, 2 x nrays, partial sums + scalars
-    size_t cell_n = 0, ray_n = 0, small_n = 0;
+    DevBuf<double> cell, ray, small;  // 5 x ncell, 2 x nrays, partial sums + scalars
   } solve;
   double t_solve_build = 0, t_solve_kernel = 0;  // last sens_op_build (whole call) / apply or solve (device), ms
   int solve_iters = 0;                           // last alifmm_sens_op_solve
@@ -293,25 +330,6 @@ static inline int fail(alifmm_ctx* c, int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return fail(ctx, ALIFMM_E_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
   } while (0)
 
-template <class T>
-static inline hipError_t dalloc(T** p, size_t n) {
-  return hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-}
-static inline void dfree(void* p) {
-  if (p) (void)hipFree(p);
-}
-// grow-only device buffer (alifmm_tfm): at least n elements
-template <class T>
-static inline hipError_t dgrow(T** p, size_t* have, size_t n) {
-  if (*p && *have >= n) return hipSuccess;
-  dfree(*p);
-  *p = nullptr;
-  *have = 0;
-  hipError_t e = dalloc(p, n);
-  if (e == hipSuccess) *have = n;
-  return e;
-}
 
-
-// slot `slot` holds an (fz, fx) field of subgrid sg (+ extra_cells doubles after it); api.cpp
+// slot `slot` holds an (fz, fx) field of subgrid sg (+ extra_cells doubles after it); host_travel.cpp
 extern "C" int af_ensure_field(alifmm_ctx* ctx, int slot, int sg, int fz, int fx, long extra_cells = 0);

@@ -1,0 +1,160 @@
+// host_ops.cpp — the module-level operators on the device: time_between_points, the local
+// operators of a batch of patches (local_ops) and the band kernel's fouds18 fallback (fouds18_band).
+#include <cstring>
+
+#include "host_internal.h"
+
+extern "C" int alifmm_time_between_points(alifmm_ctx* ctx, int n, const double* x1, const double* x2, const double* y1,
+                               const double* y2, int subgrid, double* out) {
+  if (!ctx || !ctx->have_model || n < 0 || subgrid < 1) return fail(ctx, ALIFMM_E_ARG, "time_between_points: bad args");
+  if (n == 0) return ALIFMM_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  double* d = nullptr;
+  HIPCHK(dalloc(&d, (size_t)5 * n));
+  hipError_t e = hipSuccess;
+  const double* src[4] = {x1, x2, y1, y2};
+  for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipMemcpy(d + (size_t)k * n, src[k], 8 * (size_t)n, hipMemcpyHostToDevice);
+  af::DevModel M = dev_model(ctx);
+  if (e == hipSuccess) e = af_launch_tbp(&M, n, d, d + n, d + 2 * n, d + 3 * n, ctx->dnx, subgrid, d + 4 * n, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(out, d + 4 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost);
+  dfree(d);
+  if (e != hipSuccess) return fail(ctx, ALIFMM_E_HIP, "time_between_points: %s", hipGetErrorString(e));
+  return ALIFMM_OK;
+}
+
+extern "C" int alifmm_local_ops(alifmm_ctx* ctx, int op, int n, int pz, int px, const double* ttn, const int32_t* nsts,
+                                const int32_t* iz, const int32_t* ix, const double* dnx, const double* dnz, const int32_t* nnz_arg,
+                                const int32_t* nnx_arg, const double* cell_veln, const int64_t* cell_velpn, const double* cell_vm,
+                                const int64_t* cell_stif, const double* tab, int ncol, double* out) {
+  if (!ctx || (op != 0 && op != 1) || n < 0 || pz < 1 || px < 1 || ncol < 1)
+    return fail(ctx, ALIFMM_E_ARG, "local_ops: bad args");
+  if (n == 0) return ALIFMM_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t pn = (size_t)pz * px;
+  std::vector<int> vp(n);
+  for (int k = 0; k < n; k++) vp[k] = (int)cell_velpn[k];
+  std::vector<double> st;
+  if (cell_stif) {
+    st.resize((size_t)5 * n);
+    for (size_t k = 0; k < st.size(); k++) st[k] = (double)cell_stif[k];
+  }
+  // one device block: [ttn | cveln | cvm | dnx | dnz | tab | stif | out] doubles, [nsts | iz | ix | nnz | nnx | velpn] ints
+  size_t nd = pn * n + 4 * (size_t)n + 361 * (size_t)ncol + st.size() + n;
+  size_t ni = pn * n + 5 * (size_t)n;
+  double* dd = nullptr;
+  int* di = nullptr;
+  HIPCHK(dalloc(&dd, nd));
+  if (hipMalloc((void**)&di, ni * 4) != hipSuccess) {
+    dfree(dd);
+    return fail(ctx, ALIFMM_E_HIP, "local_ops: out of memory");
+  }
+  double* p = dd;
+  af::LocalOpsParams P;
+  memset(&P, 0, sizeof P);
+  P.op = op;
+  P.n = n;
+  P.pz = pz;
+  P.px = px;
+  hipError_t e = hipSuccess;
+  auto putd = [&](const double* h, size_t cnt) {
+    double* q = p;
+    if (e == hipSuccess && cnt) e = hipMemcpy(q, h, cnt * 8, hipMemcpyHostToDevice);
+    p += cnt;
+    return (const double*)q;
+  };
+  P.ttn = putd(ttn, pn * n);
+  P.cveln = putd(cell_veln, n);
+  P.cvm = putd(cell_vm, n);
+  P.dnx = putd(dnx, n);
+  P.dnz = putd(dnz ? dnz : dnx, n);
+  P.tab = putd(tab, 361 * (size_t)ncol);
+  P.cstif = cell_stif ? putd(st.data(), st.size()) : nullptr;
+  P.out = p;
+  int* q = di;
+  auto puti = [&](const int32_t* h, size_t cnt) {
+    int* r = q;
+    if (e == hipSuccess && cnt) e = hipMemcpy(r, h, cnt * 4, hipMemcpyHostToDevice);
+    q += cnt;
+    return (const int*)r;
+  };
+  P.nsts = puti(nsts, pn * n);
+  P.iz = puti(iz, n);
+  P.ix = puti(ix, n);
+  P.nnz_arg = puti(nnz_arg, n);
+  P.nnx_arg = puti(nnx_arg, n);
+  P.cvelpn = puti(vp.data(), n);
+  P.ncol = ncol;
+  if (e == hipSuccess) e = af_launch_local_ops(&P, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(out, P.out, 8 * (size_t)n, hipMemcpyDeviceToHost);
+  dfree(dd);
+  dfree(di);
+  if (e != hipSuccess) return fail(ctx, ALIFMM_E_HIP, "local_ops: %s", hipGetErrorString(e));
+  return ALIFMM_OK;
+}
+
+extern "C" int alifmm_fouds18_band(alifmm_ctx* ctx, int n, int pz, int px, const double* ttn, const int32_t* nsts,
+                        const int32_t* iz, const int32_t* ix, const double* dnx, const double* dnz,
+                        const int32_t* nnz_arg, const int32_t* nnx_arg, const int32_t* mz, const int32_t* mx, int quant,
+                        double* out) {
+  if (!ctx || !ctx->have_model || n < 0 || pz < 1 || px < 1 || (quant != 0 && quant != 1))
+    return fail(ctx, ALIFMM_E_ARG, "fouds18_band: bad args or no model");
+  if (!ctx->dm.mid || !ctx->dm.mslo)
+    return fail(ctx, ALIFMM_E_ARG, "fouds18_band: the model has no per-material table (too many materials)");
+  for (int k = 0; k < n; k++)
+    if (mz[k] < 0 || mz[k] >= ctx->nz0 || mx[k] < 0 || mx[k] >= ctx->nx0)
+      return fail(ctx, ALIFMM_E_ARG, "fouds18_band: model cell %d (%d, %d) outside the grid", k, mz[k], mx[k]);
+  if (n == 0) return ALIFMM_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t pn = (size_t)pz * px;
+  // [ttn | dnx | dnz | out] doubles, [nsts | iz | ix | nnz | nnx | mz | mx] ints
+  double* dd = nullptr;
+  int* di = nullptr;
+  HIPCHK(dalloc(&dd, pn * n + 3 * (size_t)n));
+  if (hipMalloc((void**)&di, (pn * n + 6 * (size_t)n) * 4) != hipSuccess) {
+    dfree(dd);
+    return fail(ctx, ALIFMM_E_HIP, "fouds18_band: out of memory");
+  }
+  af::LocalOpsParams P;
+  memset(&P, 0, sizeof P);
+  P.op = 2;
+  P.n = n;
+  P.pz = pz;
+  P.px = px;
+  P.RM = dev_model(ctx);
+  P.quant = quant;
+  hipError_t e = hipSuccess;
+  double* p = dd;
+  auto putd = [&](const double* h, size_t cnt) {
+    double* q = p;
+    if (e == hipSuccess && cnt) e = hipMemcpy(q, h, cnt * 8, hipMemcpyHostToDevice);
+    p += cnt;
+    return (const double*)q;
+  };
+  int* q = di;
+  auto puti = [&](const int32_t* h, size_t cnt) {
+    int* r = q;
+    if (e == hipSuccess && cnt) e = hipMemcpy(r, h, cnt * 4, hipMemcpyHostToDevice);
+    q += cnt;
+    return (const int*)r;
+  };
+  P.ttn = putd(ttn, pn * n);
+  P.dnx = putd(dnx, n);
+  P.dnz = putd(dnz ? dnz : dnx, n);
+  P.out = p;
+  P.nsts = puti(nsts, pn * n);
+  P.iz = puti(iz, n);
+  P.ix = puti(ix, n);
+  P.nnz_arg = puti(nnz_arg, n);
+  P.nnx_arg = puti(nnx_arg, n);
+  P.mz = puti(mz, n);
+  P.mx = puti(mx, n);
+  if (e == hipSuccess) e = af_launch_local_ops(&P, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(out, P.out, 8 * (size_t)n, hipMemcpyDeviceToHost);
+  dfree(dd);
+  dfree(di);
+  if (e != hipSuccess) return fail(ctx, ALIFMM_E_HIP, "fouds18_band: %s", hipGetErrorString(e));
+  return ALIFMM_OK;
+}

@@ -1,6 +1,6 @@
 // tile_stream.h — the host side of the band kernel's field streaming (alifmm_travel_into): the
 // tile geometry of a launch and the copy threads' drain of the per-member queues.  Plain C++ (no
-// HIP), shared by api.cpp and tests/stream_sim.cpp, which drives it against a CPU model of the
+// HIP), shared by host_fields.cpp and tests/stream_sim.cpp, which drives it against a CPU model of the
 // kernel's side of the protocol (fmm_band_k.hip: tile_known / stage_tiles / publish_tiles /
 // ring_space and the end flush).
 //

@@ -340,13 +340,13 @@ int oband_seeded(int nnz, int nnx, const double *veln, const int64_t *velpn, con
     return 0;
 }
 
-/* travel_finer_grid() as the device runs it (api.cpp travel_chunk, sg > 1): the reference's two
+/* travel_finer_grid() as the device runs it (host_travel.cpp travel_chunk, sg > 1): the reference's two
  * heap stages (x9, x3) and the heap-ordered prefix of the fine main loop (fmm_exact.hip /
  * fmm_exact_lds.hip), then the band (fmm_band_k.hip mode 1) on the fine view, then / sg
  * (scale_kernel).  The stages and the hand-overs are travel_finer_impl()'s, unchanged.
  *
  * Where the device's rule decides:
- *  - tstop = (size2 + exact_r) dnx / vmax (api.cpp:893-894) with the COARSE dnx; the walk stops
+ *  - tstop = (size2 + exact_r) dnx / vmax (host_travel.cpp travel_chunk: P.tstop) with the COARSE dnx; the walk stops
  *    before popping a root with key >= tstop (fmm_exact.hip:188), also at exact_r 0 (the device has
  *    no "prefix off": tstop is then the stage-2 window's radius).
  *  - the close list handed over is the heap (fmm_exact.hip:443-447; order is irrelevant to the band:
@@ -357,9 +357,9 @@ int oband_seeded(int nnz, int nnx, const double *veln, const int64_t *velpn, con
  *    which the HBM walk runs the source again: both give the prefix modelled here.
  *  - the band: delta = cdelta dnx / vmax, t0 = r0 dnx / vmax, the far band with
  *    delta_far = cdelta_far dnx / vmax past tfar = r_far dnx / vmax only when both are > 0
- *    (fmm_band_k.hip:675-678; api.cpp:835 passes cdelta_far 0 when sg > far_sg: the caller's rule),
+ *    (fmm_band_k.hip:675-678; host_travel.cpp travel_chunk passes cdelta_far 0 when sg > far_sg: the caller's rule),
  *    update() with the coarse dnx, fouds18_A() with the coarse dnx / dnz, on the quantised fine view.
- *  - the source must lie on the coarse grid (api.cpp:882-884): -2 otherwise.
+ *  - the source must lie on the coarse grid (host_travel.cpp travel_chunk: the sg > 1 source check): -2 otherwise.
  * info[6]: band steps, nodes the prefix popped, close nodes handed over, peak heap entries of
  * stage 1, stage 2 and the prefix. */
 int oband_travel_finer(double scx, double scz, int nz0, int nx0, const double *veln, const int64_t *velpn,

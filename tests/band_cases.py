@@ -41,7 +41,7 @@ def case(name, model, shape=None, opts=None, dnx=1e-3, dnz=None, gox=0.0, goz=0.
 
 
 def vmax_of(velpn, vm, sd, vt):
-    """api.cpp set_model's vmax: the fastest group velocity over the model."""
+    """host_model.cpp set_model's vmax: the fastest group velocity over the model."""
     ang = 0.05 * np.arange(3601)
     rows = {}
     v = 0.0
@@ -57,7 +57,7 @@ def vmax_of(velpn, vm, sd, vt):
 
 
 def jump_density(veln, velpn, vm, sd):
-    """Fraction of 4-neighbour pairs whose materials differ (api.cpp material_jump)."""
+    """Fraction of 4-neighbour pairs whose materials differ (host_model.cpp set_model's jump)."""
     key = [veln, vm, velpn.astype(np.float64)]
     if sd is not None:
         key += [sd[..., k].astype(np.float64) for k in range(5)]

@@ -124,7 +124,7 @@ def model_vmax(c):
 
 
 def band_cdelta(c):
-    """context.h:208-219 band_cdelta(ctx, sg): the option if set; else from the model's jump density
+    """context.h band_cdelta(ctx, sg): the option if set; else from the model's jump density
     divided by sg (the fraction per pair of the fine grid).  get_option("cdelta") answers for
     subgrid 1 only, so this restatement is the only source of the width at subgrid > 1."""
     if "cdelta" in c.opts:
@@ -135,7 +135,7 @@ def band_cdelta(c):
 
 def lib_options(c):
     """The band options in force for a case at its subgrid (context.h band_cdelta / band_cdelta_far,
-    api.cpp:835: the far band only when sg <= far_sg): what oracle.band_travel_finer is given."""
+    host_travel.cpp travel_chunk: the far band only when sg <= far_sg): what oracle.band_travel_finer is given."""
     o = dict(LIB_DEFAULTS)
     o.update({k: v for k, v in c.opts.items() if k in o})
     cd = band_cdelta(c)
@@ -191,7 +191,7 @@ def heap_field(c, src, build=None):
 
 
 def tstop(c, vmax=None):
-    """api.cpp:893-894: the prefix's stop time, in the units of the field before the division by sg."""
+    """host_travel.cpp travel_chunk (P.tstop): the prefix's stop time, in the units of the field before the division by sg."""
     size2 = 2 * c.sg + (c.sg - 1) // 2 + 3 * c.sg
     return (size2 + lib_options(c)["exact_r"]) * c.dnx / (model_vmax(c) if vmax is None else vmax)
 

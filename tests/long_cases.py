@@ -54,7 +54,7 @@ def stream_trlog(K, wlog, nz, nx):
 
 
 def wlog_for(K, stripe_log):
-    """api.cpp travel_chunk: the stripe width follows the member count unless stripe_log fixes it."""
+    """host_travel.cpp travel_chunk: the stripe width follows the member count unless stripe_log fixes it."""
     return stripe_log if stripe_log else (4 if K >= 16 else 5 if K >= 8 else 6)
 
 
@@ -242,7 +242,7 @@ RAGGED_CASES = [LongCase("ragged_%s" % n, "travel", "grain1200", RAGGED_N, RAGGE
 MIXED_CENSUS_CASE = LongCase("mixed_600_centre", "travel", "mixed", 600, 600, (300, 300), ((0, 2),), ())
 
 # capacity: 16 members of 8-column stripes on 128 columns.  The work lists hold max(65536, cells / 8)
-# entries per source (api.cpp travel_chunk), a 16th of it per member: 4096 on both grids.
+# entries per source (host_travel.cpp travel_chunk), a 16th of it per member: 4096 on both grids.
 # loud: a full column of seeds at column 3 hands member 0 the 7800 close cells of columns 2 and 4.
 # (3900 rows, not more: 3 x 3900 = 11 700 seeds and close cells of the hand-over's 11 881.)
 CAP_LOUD = LongCase("cap_loud_3900x128", "col", "iso", 3900, 128, 3, ((3, 16),), ())

@@ -198,7 +198,7 @@ def test_every_member_count_gives_one_members_bits(ctx, envelope, case, geoms):
 @pytest.mark.parametrize("case,slog,K,kept", BC.NARROW_CASES, ids=lambda v: getattr(v, "name", None))
 def test_more_members_than_stripes_is_clamped(ctx, envelope, case, slog, K, kept):
     """16 members asked for on a grid of one (65 x 3) or two (61 x 65) 64-column stripes: the host
-    lowers the count to the stripe count (api.cpp choose_members; a member without a stripe would
+    lowers the count to the stripe count (host_travel.cpp choose_members; a member without a stripe would
     still take its 1 / K share of the work-list capacity from the members that own cells), and the
     run gives the one-member bits and the model's field."""
     opt, vmax = _set_model(ctx, case)

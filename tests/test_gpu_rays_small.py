@@ -1,4 +1,4 @@
-"""The ray tracer (csrc/rays.hip find_ray_kernel / tbp_wave, utils.hip tbp_kernel, api.cpp
+"""The ray tracer (csrc/rays.hip find_ray_kernel / tbp_wave, utils.hip tbp_kernel, host_rays.cpp
 alifmm_find_rays) against the CPU oracle on the small-shape matrix of tests/ray_cases.py.  Every
 field is uploaded (alifmm_put_field), so the ray kernel runs on exactly known fields, independent of
 the band kernel.  Run on the GPU box: pytest -m gpu.
@@ -148,7 +148,7 @@ def _same(a, b, ia=None, ib=None):
 
 
 def _fill9(c):
-    """Rays from which a request gets 9-lane groups (api.cpp alifmm_find_rays fill9)."""
+    """Rays from which a request gets 9-lane groups (host_rays.cpp alifmm_find_rays fill9)."""
     return int(c.get_option("n_cu")) * 4 * int(c.get_option("ray_waves_per_simd")) * 7
 
 

@@ -1,4 +1,4 @@
-"""Travel-time sensitivities along rays on the device (csrc/ray_sens.hip, api.cpp alifmm_ray_sens,
+"""Travel-time sensitivities along rays on the device (csrc/ray_sens.hip, host_sens.cpp alifmm_ray_sens,
 Context.ray_sens, ALI_FMM.ray_sensitivity) against the Python restatement of the contract
 (tests/sens_ref.py, pinned to the oracle by tests/test_sens_ref.py) with the correctly rounded build
 of the oracle.  Fields are uploaded (alifmm_put_field) where rays are traced.  Run: pytest -m gpu.

@@ -1,4 +1,4 @@
-"""The resident sensitivity operator on the device (csrc/sens_solve.hip, api.cpp alifmm_sens_op_*,
+"""The resident sensitivity operator on the device (csrc/sens_solve.hip, host_sens.cpp alifmm_sens_op_*,
 Context.sens_op_*, ALI_FMM.tomography_step) against the numpy restatement (tests/solve_ref.py, held
 to numpy's lstsq by tests/test_solve_ref.py).  Run: pytest -m gpu.
 

@@ -1,4 +1,4 @@
-"""Back-wall echo paths between element pairs on the device (csrc/skip_pairs.hip, api.cpp
+"""Back-wall echo paths between element pairs on the device (csrc/skip_pairs.hip, host_rays.cpp
 alifmm_skip_pick / alifmm_skip_rays, Context.skip_pick / skip_rays, ALI_FMM.find_all_skip_rays)
 against the numpy restatement tests/skip_ref.py, the host composition of two alifmm_find_rays calls,
 the CPU oracle and tests/sens_ref.py.  Fields are uploaded (alifmm_put_field) wherever the bits

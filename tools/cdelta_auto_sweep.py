@@ -1,4 +1,4 @@
-"""CPU sweep behind the automatic band width (api.cpp band_cdelta): the band formulation's field
+"""CPU sweep behind the automatic band width (context.h band_cdelta): the band formulation's field
 error against the heap oracle as a function of the model's material-interface density and cdelta.
 Runs the CPU band model (oracle/band_model.c, which the device matches to 1e-9) and the heap
 oracle on small models: per-cell random orientations, random-orientation blocks of g x g cells,

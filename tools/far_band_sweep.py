@@ -23,7 +23,7 @@ SCHEDULES = [(0.0, 0.0), (0.75, 256.0), (1.0, 256.0), (0.75, 512.0), (1.0, 512.0
 
 
 def vmax_of(velpn, vm, sd, vt):
-    """The host's band-width scale (api.cpp alifmm_set_model): fastest group speed in the model."""
+    """The host's band-width scale (host_model.cpp alifmm_set_model): fastest group speed in the model."""
     v = 0.0
     cols = vt[:181, 1:].max(axis=0)
     tab = velpn != 0
