@@ -125,6 +125,7 @@ struct Lds {
   int xl;  // every member of the source on this member's XCD (set by the exchange)
   int takenb[2], nRb[2];  // [step parity]: fresh close-set slots taken by the commit; rim-list length
   int nrim[2];  // rim-list lengths of the neighbour members (left, right) this step
+  int evq;  // P4: the next chunk of 64 claimed cells to hand out (its index in the claimed list)
 };
 
 
@@ -538,7 +539,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
   double* const rimt = B->rimt;
   // edge buffer of parity p: Tb + tb_cells + p * ecells, compact (KGeom::eidx)
   const int cells = nz * nx, ecells = (int)P.ecells, tbc = (int)P.tb_cells;
-  double* const E0 = Tb + tbc;
+  // (uniform: held in scalar registers; as a vector pair it was the value spilled once P4's
+  // hand-out changed the allocation, 80 instead of 72 bytes of scratch per lane)
+  double* const E0 = reinterpret_cast<double*>(bcast64(reinterpret_cast<unsigned long long>(Tb + tbc), 0));
   // host streaming (mode 0 only)
   const bool hstream = MODE == 0 && P.hs != nullptr;
   TileStream ts{};
@@ -734,6 +737,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
       sh->nA = 0;
       sh->nE2 = 0;
       sh->nFb = 0;
+      sh->evq = kThreads;  // (its last use, the last step's P4, is behind two barriers)
       sh->takenb[par] = 0;
       sh->nRx = 0;
       sh->nDb[par] = 0;  // (the last step's P0 read nDb[prv])
@@ -1098,9 +1102,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
       }
     };
     // stencil loads first, then the material id: one memory round trip per cell.  The boundary
-    // cells (the list's tail) go last (first measured slower).  Every wave whose
-    // cells are all interior loads T only.
-    for (int e = tid; e < nE; e += kThreads) {
+    // cells (the list's tail) go last (first measured slower, under the static and under the
+    // dynamic hand-out).  Every wave whose cells are all interior loads T only.
+    // Chunks of 64 cells: a wave's first is the one at its own index, every further one comes from
+    // the LDS counter as the wave comes free (a wave that met a slow path of cr_math.h then takes
+    // fewer).  A Jacobi pass: which wave evaluates a chunk changes no value, and the fallback
+    // list's order depended on atomic timing before.  A step of at most kThreads cells never
+    // touches the counter.
+    for (int e = tid; e < nE;) {
       const bool interior = e - lane + 64 <= nEi;  // (wave-uniform)
       const int r = lds_e ? cellE(e, std::true_type{}) : cellE(e, std::false_type{});
       const int z = pkz(r), x = pkx(r);
@@ -1109,6 +1118,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(3))) v
       else load_nb(nb, Tb, TL, eprv, tbc + 2 * ecells, g, z, x);
       const CellMat cm = band_mat<LDSMAT, MODE == 0>(M, sh->mat, sh->stab, R.mv, z, x);
       eval_done(e, update(nb, M, cm, z, x, dnx_e, nz, nx));
+      int e0 = e - lane + kThreads;
+      if (nE > kThreads) {  // (uniform)
+        if (lane == 0) e0 = atomicAdd(&sh->evq, 64);
+        e0 = __builtin_amdgcn_readfirstlane(e0);  // (lane 0 holds the chunk's lowest index: it is active)
+      }
+      e = e0 + lane;
     }
     AF_TICK(3)
     // ---- P4b: fouds18_A() over the compacted fallback list, in staged rounds ----
