@@ -716,11 +716,16 @@ class ALI_FMM:
 
     def lsq_image(self, fmc, fs, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1, veln=None,
                   velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct", reflector=None, damp=0.0,
-                  smooth=0.0, max_iter=50, tol=1e-6):
+                  smooth=0.0, max_iter=50, tol=1e-6, pulse=None, pulse_origin=0):
         """Least-squares image of full-matrix-capture data: the reflectivity map x on the pixel
         window that minimises |simulate_fmc(x) - fmc|² + damp² |x|² + smooth² |D x|², by CGLS from
         x = 0 (no counterpart in the reference).  A is simulate_fmc() without a pulse, Aᵀ is tfm()
         on float64 data, D the first difference between 4-neighbour pixels.
+        pulse: None, or the transducer's pulse (1-D real or complex, at most 1024 taps; a complex
+        pulse needs complex data).  The model is then simulate_fmc(x, pulse=pulse): the per-trace
+        convolution and its exact transpose run on the device inside the iteration
+        (_alifmm.Context.trace_fir).  pulse_origin is the tap index of the pulse's time zero; 0 is
+        simulate_fmc's convention.  Measured data need the pulse: without it the solve fits spikes.
 
         fmc, fs, t0, tx, rx, weights, window, step, subgrid_size, the model arguments, tx_path,
         rx_path and reflector: as in tfm(), with the same field computation and the same checks;
@@ -737,7 +742,8 @@ class ALI_FMM:
         txs, rxs = self._pair_slots("lsq_image", tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path, rx_path,
                                     reflector)
         return self._ctx(0).tfm_lsq(txs, rxs, fmc, fs, t0=t0, weights=weights, window=window, step=step,
-                                    subgrid=int(subgrid_size), damp=damp, smooth=smooth, max_iter=max_iter, tol=tol)
+                                    subgrid=int(subgrid_size), damp=damp, smooth=smooth, max_iter=max_iter, tol=tol,
+                                    pulse=pulse, pulse_origin=pulse_origin)
 
     def simulate_fmc(self, refl, fs, nt, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1,
                      veln=None, velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct",
@@ -754,7 +760,7 @@ class ALI_FMM:
         stay on the device, _alifmm.Context.tfm_model reads them there) and the same checks.
         pulse: 1-D real or complex wavelet applied on the host after the call,
         out[..., k] = sum_j pulse[j] d[..., k - j], truncated to nt (numpy's FFT in float64; the
-        device does not convolve).
+        device does not convolve).  lsq_image(pulse=pulse) inverts such data (pulse_origin 0).
         Returns float64 (len(tx), len(rx), nt), or complex128 when refl or pulse is complex.  The
         order of the device's sums is not fixed: two calls agree to rounding, not to the bit.
 

@@ -90,6 +90,9 @@ def _load():
             "alifmm_tfm_coh": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
             "alifmm_tfm_lsq": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _d, _d, _i, _d,
                                     _p, _p, _p]),
+            "alifmm_tfm_lsq_pulse": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _d, _d, _i,
+                                          _d, _i, _i, _p, _i, _p, _p, _p]),
+            "alifmm_trace_fir": (_i, [_p, _l, _i, _i, _p, _i, _i, _p, _i, _i, _p]),
             "alifmm_ray_sens": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p]),
             "alifmm_sens_op_build": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
             "alifmm_sens_op_apply": (_i, [_p, _i, _p, _p]),
@@ -421,8 +424,45 @@ class Context:
         image = img.view(np.complex128)[..., 0] if cplx else img[..., 0]
         return (image, fac, raw) if sums else (image, fac)
 
+    @staticmethod
+    def _pulse_args(what, pulse, cplx_data):
+        """A 1-D real or complex pulse -> its taps, float64 (ntap, tap_comp)."""
+        pulse = np.asarray(pulse)
+        if pulse.ndim != 1:
+            raise ValueError("%s: pulse must be a 1-D array, not %s" % (what, pulse.shape))
+        if np.iscomplexobj(pulse):
+            if not cplx_data:
+                raise ValueError("%s: a complex pulse needs complex data" % what)
+            return np.ascontiguousarray(pulse, dtype=np.complex128).view(np.float64).reshape(-1, 2)
+        return np.ascontiguousarray(pulse, dtype=np.float64).reshape(-1, 1)
+
+    def trace_fir(self, data, pulse, origin=0, transpose=False):
+        """Every trace of data convolved with one pulse on the device (alifmm_trace_fir), or, with
+        transpose=True, correlated with it: the exact transpose of the same linear map.
+        out[..., t] = sum_j pulse[j] data[..., t - j + origin], j ascending, samples outside the
+        trace adding nothing; transposed, out[..., t] = sum_j conj(pulse[j]) data[..., t + j - origin].
+        All in float64 in a fixed order: the result is reproducible to the bit and a trace does not
+        depend on the others.
+
+        data: (..., nt) real or complex, sent as float64.  pulse: 1-D real or complex, at most 1024
+        finite taps; a complex pulse needs complex data.  origin: the tap index of the pulse's time
+        zero (0: causal, the convention of ALI_FMM.simulate_fmc).
+        Returns float64, or complex128 for complex data, of data's shape."""
+        data = np.asarray(data)
+        if data.ndim < 1:
+            raise ValueError("trace_fir: data must have shape (..., nt)")
+        cplx = np.iscomplexobj(data)
+        taps = self._pulse_args("trace_fir", pulse, cplx)
+        x = np.ascontiguousarray(data, dtype=np.complex128 if cplx else np.float64)
+        nc = 2 if cplx else 1
+        nt = x.shape[-1]
+        out = np.empty(x.shape + (nc,))
+        self._chk(lib().alifmm_trace_fir(self._h, x.size // nt if nt else 0, nt, nc, _ptr(x), taps.shape[0], taps.shape[1],
+                                         _ptr(taps), int(origin), int(bool(transpose)), _ptr(out)), "trace_fir")
+        return out.view(np.complex128)[..., 0] if cplx else out[..., 0]
+
     def tfm_lsq(self, tx_slots, rx_slots, fmc, fs, t0=0.0, weights=None, window=None, step=1, subgrid=1, damp=0.0,
-                smooth=0.0, max_iter=50, tol=1e-6, resid=False):
+                smooth=0.0, max_iter=50, tol=1e-6, resid=False, pulse=None, pulse_origin=0):
         """Least-squares image of full-matrix-capture data over resident fields (alifmm_tfm_lsq):
         CGLS from x = 0 on min |A x - fmc|² + damp² |x|² + smooth² |D x|², A being tfm_model() on
         the dense window, Aᵀ tfm(precision="f64") and D the first difference between 4-neighbour
@@ -433,6 +473,11 @@ class Context:
         tx_slots, rx_slots, fs, t0, weights, window, step, subgrid: as in tfm().  fmc: (ntx, nrx,
         nt) real or complex, every value finite, sent as float64.  damp is absolute (|A|_2 is of the
         order sqrt(ntx nrx)).
+        pulse: None, or the transducer's pulse, 1-D real or complex (complex: complex data), at
+        most 1024 finite taps, with pulse_origin the tap index of its time zero.  The operator is
+        then P A (alifmm_tfm_lsq_pulse), P being trace_fir(., pulse, pulse_origin) on every trace:
+        the model of measured data, which are the spike trains of tfm_model() convolved with the
+        pulse.  grad0 = |Aᵀ Pᵀ fmc|, and the residual is fmc - P A x.
         Returns (image, info), or (image, info, resid) with resid=True (the recurred residual, the
         shape of fmc): image float64 (niz, nix) or complex128 for complex data; info =
         dict(iterations, grad0 = |Aᵀ fmc|, grad, rhs_norm, res_norm, reason ("tol", "max_iter" or
@@ -445,10 +490,14 @@ class Context:
         img = np.zeros((max(niz, 0), max(nix, 0), nc))
         res = np.zeros(data.shape + (nc,)) if resid else None
         info = np.zeros(8)
-        self._chk(lib().alifmm_tfm_lsq(self._h, int(subgrid), len(tx), _ptr(tx), len(rx), _ptr(rx), _ptr(data),
-                                       data.shape[2], nc, float(t0), float(fs), _ptr(w), iz0, ix0, niz, nix, step,
-                                       float(damp), float(smooth), int(max_iter), float(tol), _ptr(img), _ptr(res),
-                                       _ptr(info)), "tfm_lsq")
+        head = (self._h, int(subgrid), len(tx), _ptr(tx), len(rx), _ptr(rx), _ptr(data), data.shape[2], nc, float(t0),
+                float(fs), _ptr(w), iz0, ix0, niz, nix, step, float(damp), float(smooth), int(max_iter), float(tol))
+        if pulse is None:
+            self._chk(lib().alifmm_tfm_lsq(*head, _ptr(img), _ptr(res), _ptr(info)), "tfm_lsq")
+        else:
+            taps = self._pulse_args("tfm_lsq", pulse, cplx)
+            self._chk(lib().alifmm_tfm_lsq_pulse(*head, taps.shape[0], taps.shape[1], _ptr(taps), int(pulse_origin),
+                                                 _ptr(img), _ptr(res), _ptr(info)), "tfm_lsq")
         out = {"iterations": int(info[0]), "grad0": info[1], "grad": info[2], "rhs_norm": info[3], "res_norm": info[4],
                "reason": self.SOLVE_REASONS[int(info[5])]}
         image = img.view(np.complex128)[..., 0] if cplx else img[..., 0]

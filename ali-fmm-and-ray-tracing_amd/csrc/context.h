@@ -257,17 +257,23 @@ struct alifmm_ctx {
   int tfm_model_combine = 12;  // a wave of at most this many runs of lanes sharing a sample sums each run before it adds
   int tfm_model_tile_used = 0, tfm_model_slabs_used = 0;  // what the last alifmm_tfm_model ran with
   double t_tfm_model_upload = 0, t_tfm_model_kernel = 0;  // last alifmm_tfm_model (ms)
-  // alifmm_tfm_lsq: grow-only device buffers (r and q: 2 x the data; x, p, s and t: 4 x the image;
-  // the window's pixel list, pair weights, slot pointer table, partial sums + scalars), freed with
-  // the context, or by a call whose allocation fails
+  // alifmm_tfm_lsq: grow-only device buffers (r and q: 2 x the data, and w with a pulse: 3 x; x, p, s
+  // and t: 4 x the image; the window's pixel list, pair weights, slot pointer table, partial sums +
+  // scalars), freed with the context, or by a call whose allocation fails
   struct TfmLsqBufs {
     DevBuf<double> data, img, small;
     DevBuf<int64_t> pix;
     DevBuf<float> w;
     DevBuf<const double*> tab;
   } tfm_lsq;
-  double t_tfm_lsq_upload = 0, t_tfm_lsq_kernel = 0;  // last alifmm_tfm_lsq (ms)
+  double t_tfm_lsq_upload = 0, t_tfm_lsq_kernel = 0;  // last alifmm_tfm_lsq / alifmm_tfm_lsq_pulse (ms)
   int tfm_lsq_iters = 0;
+  // alifmm_trace_fir: grow-only device buffers (the traces in and out, the taps; the taps also serve
+  // alifmm_tfm_lsq_pulse), freed with the context
+  struct FirBufs {
+    DevBuf<double> in, out, taps;
+  } fir;
+  double t_fir_upload = 0, t_fir_kernel = 0;  // last alifmm_trace_fir (ms)
   // alifmm_ray_sens: grow-only device buffers (a chunk of host points, the per-ray arrays of a
   // request, the three maps), freed with the context; the row arrays live for one call
   struct SensBufs {

@@ -79,6 +79,7 @@ extern "C" int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   ctx->seed = {};
   ctx->tfm = {};
   ctx->tfm_lsq = {};
+  ctx->fir = {};
   ctx->tfm_model = {};
   ctx->skip = {};
   ctx->sens = {};
@@ -197,6 +198,11 @@ extern "C" int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* valu
   else if (!strcmp(name, "tfm_lsq_upload_ms")) *value = ctx->t_tfm_lsq_upload;
   else if (!strcmp(name, "tfm_lsq_kernel_ms")) *value = ctx->t_tfm_lsq_kernel;
   else if (!strcmp(name, "tfm_lsq_iters")) *value = ctx->tfm_lsq_iters;
+  // last alifmm_trace_fir call (ms): host -> device copies (host clock), the kernel (HIP events); the
+  // outputs per workgroup of the kernel (a constant of the build)
+  else if (!strcmp(name, "trace_fir_upload_ms")) *value = ctx->t_fir_upload;
+  else if (!strcmp(name, "trace_fir_kernel_ms")) *value = ctx->t_fir_kernel;
+  else if (!strcmp(name, "trace_fir_tile")) *value = af_trace_fir_tile();
   // last alifmm_travel_seeded call: the seed pass (uploads and fmm_seed_kernel, HIP events, ms), the
   // seeds and the close cells handed over per field
   else if (!strcmp(name, "seed_ms")) *value = ctx->t_seed;

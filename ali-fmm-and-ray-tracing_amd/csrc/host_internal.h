@@ -42,6 +42,17 @@ int d2h_pageable(alifmm_ctx* ctx, const std::vector<D2HSeg>& segs);
 // ---- host_rays.cpp ----
 void release_kept_rays(alifmm_ctx* c);  // points kept by alifmm_find_rays(..., ALIFMM_KEEP_RAYS)
 
+// ---- host_fir.cpp ----
+// the taps of a trace FIR as an entry point takes them: taps[ntap][tap_comp] on the host
+struct FirTaps {
+  int ntap, tap_comp;
+  const double* taps;
+  int origin;
+};
+// the tap conditions of alifmm_trace_fir and alifmm_tfm_lsq_pulse (`what` names the caller) against
+// data of ncomp components
+int fir_check_taps(alifmm_ctx* ctx, const char* what, int ncomp, const FirTaps& F);
+
 // ---- timed sections ----
 // `launch(stream)` between the context's first two events, waited for; its device time into *ms
 template <class F>

@@ -1,7 +1,8 @@
 // host_tfm.cpp — the TFM family over resident fields: alifmm_tfm / _f64 / _coh (delay and sum),
 // alifmm_tfm_model (its transpose) and alifmm_tfm_lsq (the least-squares solve on both).  One front
 // half: the checks (tfm_check), the parameter blocks (tfm_params, tfm_model_params) and the
-// modelling kernel's launch plan (tfm_model_plan).
+// modelling kernel's launch plan (tfm_model_plan).  alifmm_tfm_lsq_pulse is the same solve with the
+// trace FIR (host_fir.cpp, trace_fir.hip) around the two products.
 #include <chrono>
 
 #include "host_internal.h"
@@ -273,11 +274,14 @@ extern "C" int alifmm_tfm_model(alifmm_ctx* ctx, int subgrid, int ntx, const int
   return ALIFMM_OK;
 }
 
-// The device half of alifmm_tfm_lsq, after the checks: hipSuccess or the first error (the caller
-// frees the call's buffers on one)
+// The device half of alifmm_tfm_lsq (F null) and of alifmm_tfm_lsq_pulse (F: the pulse), after the
+// checks: hipSuccess or the first error (the caller frees the call's buffers on one).  With a pulse
+// the operator is P A: a third data-sized vector w lies between the FIR and the two products
+// (A writes it, Aᵀ reads it), q = P w and w = Pᵀ r.
 static hipError_t tfm_lsq_run(alifmm_ctx* ctx, const std::vector<const double*>& tab, const TfmCall& C,
-                              const TfmModelPlan& plan, const double* fmc, const float* pair_w, double damp, double smooth,
-                              int max_iter, double tol, double* image, double* resid, CglsResult* R) {
+                              const TfmModelPlan& plan, const FirTaps* F, const double* fmc, const float* pair_w,
+                              double damp, double smooth, int max_iter, double tol, double* image, double* resid,
+                              CglsResult* R) {
 #define LSQ(call)                    \
   do {                               \
     hipError_t e_ = (call);          \
@@ -286,12 +290,13 @@ static hipError_t tfm_lsq_run(alifmm_ctx* ctx, const std::vector<const double*>&
   const size_t npix = C.nwin(), nd = C.ndata(), ni = npix * C.ncomp;
   LSQ(hipSetDevice(ctx->device));
   alifmm_ctx::TfmLsqBufs& B = ctx->tfm_lsq;
-  LSQ(B.data.grow(2 * nd));
+  LSQ(B.data.grow((F ? 3 : 2) * nd));
   LSQ(B.img.grow(4 * ni));
   LSQ(B.small.grow((size_t)af::kSolveMaxParts + af::kSolScalars));
   LSQ(B.pix.grow(npix));
   if (pair_w) LSQ(B.w.grow(C.npair()));
   LSQ(B.tab.grow(tab.size()));
+  if (F) LSQ(ctx->fir.taps.grow((size_t)F->ntap * F->tap_comp));
   af::SolveVecs V;
   V.x = B.img;
   V.p = B.img + ni;
@@ -304,8 +309,11 @@ static hipError_t tfm_lsq_run(alifmm_ctx* ctx, const std::vector<const double*>&
   V.scal = B.small + af::kSolveMaxParts;
   V.damp2 = damp * damp;
   V.smooth2 = smooth * smooth;
+  double* const aq = F ? B.data + 2 * nd : V.q;        // what A writes: q, or w with a pulse
+  const double* const atr = F ? B.data + 2 * nd : V.r;  // what Aᵀ reads: r, or w = Pᵀ r
   const auto c0 = std::chrono::steady_clock::now();
   LSQ(hipMemcpy(V.r, fmc, nd * sizeof(double), hipMemcpyHostToDevice));
+  if (F) LSQ(hipMemcpy(ctx->fir.taps, F->taps, (size_t)F->ntap * F->tap_comp * sizeof(double), hipMemcpyHostToDevice));
   if (pair_w) LSQ(hipMemcpy(B.w, pair_w, C.npair() * sizeof(float), hipMemcpyHostToDevice));
   LSQ(hipMemcpy(B.tab, tab.data(), tab.size() * sizeof(double*), hipMemcpyHostToDevice));
   ctx->t_tfm_lsq_upload = ms_since(c0);
@@ -316,21 +324,33 @@ static hipError_t tfm_lsq_run(alifmm_ctx* ctx, const std::vector<const double*>&
   G.nimg = (int64_t)ni;
   G.ndata = (int64_t)nd;
   const float* w = pair_w ? B.w.p : nullptr;
-  const af::TfmParams T = tfm_params(C, B.tab, nullptr, V.r, w, V.t);                            // t = Aᵀ r
-  const af::TfmModelParams M = tfm_model_params(ctx, C, plan, B.tab, B.pix, npix, V.p, w, V.q);  // q = A p
+  const af::TfmParams T = tfm_params(C, B.tab, nullptr, atr, w, V.t);                           // t = Aᵀ r
+  const af::TfmModelParams M = tfm_model_params(ctx, C, plan, B.tab, B.pix, npix, V.p, w, aq);  // q = A p
   hipStream_t st = ctx->stream;
   const int chunk = ctx->tfm_chunk;
+  // q = P w (transpose 0) or w = Pᵀ r (1) over the ntx nrx traces; nothing without a pulse
+  const auto fir = [&](int transpose) {
+    if (!F) return hipSuccess;
+    const af::TraceFirParams Q{transpose ? V.r : aq, transpose ? aq : V.q, ctx->fir.taps, (int64_t)C.npair(),
+                               C.nt, F->ntap, F->origin, transpose};
+    return af_launch_trace_fir(&Q, C.ncomp, F->tap_comp, st);
+  };
+  const auto form_t = [&] {
+    hipError_t e = fir(1);
+    return e == hipSuccess ? af_launch_tfm_f64(&T, chunk, st) : e;
+  };
   LSQ(hipEventRecord(ctx->ev[0], st));
   LSQ(af_launch_tfm_lsq_pix(C.iz0, C.ix0, C.step, C.fx, C.niz, C.nix, B.pix, st));
   LSQ(cgls_run(
-      V, ni, nd, st, ctx->ev[0], ctx->ev[1], max_iter, tol, [&] { return af_launch_tfm_f64(&T, chunk, st); },
+      V, ni, nd, st, ctx->ev[0], ctx->ev[1], max_iter, tol, form_t,
       [&] { return af_launch_tfm_lsq_grad(&G, &V, 1, st); },  // x = 0: s = Aᵀ d, p = s, gamma_0 = |s|²
       [&] {
-        // several slabs add into q with atomics: zeroed every iteration
-        hipError_t e = plan.slabs > 1 ? hipMemsetAsync(V.q, 0, nd * sizeof(double), st) : hipSuccess;
+        // several slabs add into q (with a pulse: w) with atomics: zeroed every iteration
+        hipError_t e = plan.slabs > 1 ? hipMemsetAsync(aq, 0, nd * sizeof(double), st) : hipSuccess;
         if (e == hipSuccess) e = af_launch_tfm_model(&M, st);
+        if (e == hipSuccess) e = fir(0);
         if (e == hipSuccess) e = af_launch_tfm_lsq_step(&G, &V, st);
-        if (e == hipSuccess) e = af_launch_tfm_f64(&T, chunk, st);
+        if (e == hipSuccess) e = form_t();
         if (e == hipSuccess) e = af_launch_tfm_lsq_grad(&G, &V, 0, st);
         return e;
       },
@@ -342,29 +362,50 @@ static hipError_t tfm_lsq_run(alifmm_ctx* ctx, const std::vector<const double*>&
 #undef LSQ
 }
 
+// alifmm_tfm_lsq (F null) and alifmm_tfm_lsq_pulse: the checks, the plan, the solve
+static int tfm_lsq_impl(alifmm_ctx* ctx, const char* what, int subgrid, const int32_t* tx_slot, const int32_t* rx_slot,
+                        const double* fmc, const float* pair_w, TfmCall C, const FirTaps* F, double damp, double smooth,
+                        int max_iter, double tol, double* image, double* resid, double* info8) {
+  if (!ctx) return ALIFMM_E_ARG;
+  std::vector<const double*> tab;
+  if (int rc = tfm_check(ctx, what, subgrid, tx_slot, rx_slot, fmc, image, C, tab)) return rc;
+  if (!info8) return fail(ctx, ALIFMM_E_ARG, "%s: info8 is NULL", what);
+  if (int rc = cgls_check(ctx, what, damp, smooth, max_iter, tol)) return rc;
+  if (F)
+    if (int rc = fir_check_taps(ctx, what, C.ncomp, *F)) return rc;
+  const size_t nd = C.ndata();
+  for (size_t k = 0; k < nd; k++)
+    if (!std::isfinite(fmc[k])) return fail(ctx, ALIFMM_E_ARG, "%s: fmc[%zu] is not finite", what, k);
+  // the modelling kernel's plan (alifmm_tfm_model), every pixel of the window counting
+  TfmModelPlan plan;
+  if (int rc = tfm_model_plan(ctx, what, C, C.nwin(), &plan)) return rc;
+  CglsResult R;
+  const hipError_t e = tfm_lsq_run(ctx, tab, C, plan, F, fmc, pair_w, damp, smooth, max_iter, tol, image, resid, &R);
+  if (e != hipSuccess) {  // (out of memory, for one): the call's buffers go
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->tfm_lsq = {};
+    return fail(ctx, ALIFMM_E_HIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  R.pack(info8, 0.0);
+  return ALIFMM_OK;
+}
+
 extern "C" int alifmm_tfm_lsq(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx,
                               const int32_t* rx_slot, const double* fmc, int nt, int ncomp, double t0, double fs,
                               const float* pair_w, int iz0, int ix0, int niz, int nix, int step, double damp,
                               double smooth, int max_iter, double tol, double* image, double* resid, double* info8) {
-  if (!ctx) return ALIFMM_E_ARG;
-  TfmCall C{ntx, nrx, nt, ncomp, t0, fs, iz0, ix0, niz, nix, step, 0};
-  std::vector<const double*> tab;
-  if (int rc = tfm_check(ctx, "tfm_lsq", subgrid, tx_slot, rx_slot, fmc, image, C, tab)) return rc;
-  if (!info8) return fail(ctx, ALIFMM_E_ARG, "tfm_lsq: info8 is NULL");
-  if (int rc = cgls_check(ctx, "tfm_lsq", damp, smooth, max_iter, tol)) return rc;
-  const size_t nd = C.ndata();
-  for (size_t k = 0; k < nd; k++)
-    if (!std::isfinite(fmc[k])) return fail(ctx, ALIFMM_E_ARG, "tfm_lsq: fmc[%zu] is not finite", k);
-  // the modelling kernel's plan (alifmm_tfm_model), every pixel of the window counting
-  TfmModelPlan plan;
-  if (int rc = tfm_model_plan(ctx, "tfm_lsq", C, C.nwin(), &plan)) return rc;
-  CglsResult R;
-  const hipError_t e = tfm_lsq_run(ctx, tab, C, plan, fmc, pair_w, damp, smooth, max_iter, tol, image, resid, &R);
-  if (e != hipSuccess) {  // (out of memory, for one): the call's buffers go
-    (void)hipStreamSynchronize(ctx->stream);
-    ctx->tfm_lsq = {};
-    return fail(ctx, ALIFMM_E_HIP, "tfm_lsq: %s", hipGetErrorString(e));
-  }
-  R.pack(info8, 0.0);
-  return ALIFMM_OK;
+  return tfm_lsq_impl(ctx, "tfm_lsq", subgrid, tx_slot, rx_slot, fmc, pair_w,
+                      {ntx, nrx, nt, ncomp, t0, fs, iz0, ix0, niz, nix, step, 0}, nullptr, damp, smooth, max_iter, tol,
+                      image, resid, info8);
+}
+
+extern "C" int alifmm_tfm_lsq_pulse(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx,
+                                    const int32_t* rx_slot, const double* fmc, int nt, int ncomp, double t0, double fs,
+                                    const float* pair_w, int iz0, int ix0, int niz, int nix, int step, double damp,
+                                    double smooth, int max_iter, double tol, int ntap, int tap_comp, const double* taps,
+                                    int origin, double* image, double* resid, double* info8) {
+  const FirTaps F{ntap, tap_comp, taps, origin};
+  return tfm_lsq_impl(ctx, "tfm_lsq_pulse", subgrid, tx_slot, rx_slot, fmc, pair_w,
+                      {ntx, nrx, nt, ncomp, t0, fs, iz0, ix0, niz, nix, step, 0}, &F, damp, smooth, max_iter, tol, image,
+                      resid, info8);
 }

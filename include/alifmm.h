@@ -478,6 +478,70 @@ int alifmm_tfm_lsq(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot
                    int niz, int nix, int step, double damp, double smooth, int max_iter, double tol, double* image,
                    double* resid, double* info8);
 
+/* The trace FIR P and its exact transpose P^T: every trace convolved with one pulse (transpose:
+ * correlated with it), on the device in a fixed order.  Measured FMC data are the spike trains of
+ * alifmm_tfm_model convolved with the transducer's pulse; P is that step as a linear operator.
+ *   in                 float64 [ntrace][nt][ncomp], ncomp 1 (real) or 2 (re, im interleaved)
+ *   taps               the pulse h, float64 [ntap][tap_comp]: tap_comp 1 real taps, applied to each
+ *                      component; 2 complex taps (re, im), ncomp 2 only; every value finite
+ *   origin             the tap index of the pulse's time zero, 0 <= origin < ntap (0: a causal pulse,
+ *                      out[k] = sum_j h[j] in[k - j])
+ *   transpose          0: out = P in; 1: out = P^T in
+ *   out                float64, the shape of in; may be in itself
+ * Per trace and output sample t, all in float64, operations in the order written, no contraction:
+ *   forward    y[t] = sum over j = 0 .. ntap - 1, ascending, of h[j] * x[t - j + origin]
+ *   transpose  z[t] = sum over j ascending of conj(h[j]) * y[t + j - origin]
+ *   the accumulator starts at +0.0 per component; a sample index outside 0 .. nt - 1 adds nothing
+ *   real tap     acc_c += h * x_c (one multiply, one add) for each component c
+ *   complex tap  pr = (hr * xr) - (hi * xi); pi = (hr * xi) + (hi * xr); acc_r += pr; acc_i += pi;
+ *                the transpose negates hi first
+ * So the outputs are bit-reproducible, a trace's result does not depend on the other traces of the
+ * call, and <P x, y> = <x, P^T y> to rounding under the real inner product (P^T is the transpose of
+ * the real matrix of P on interleaved components).  The data are not checked: a non-finite sample
+ * propagates to the outputs it reaches.
+ * ALIFMM_E_ARG with a message, the context staying usable and nothing written: ctx, in, taps or out
+ * NULL; ntrace < 1; nt < 1; ncomp or tap_comp not 1 or 2; tap_comp 2 with ncomp 1; ntap < 1 or
+ * ntap > ALIFMM_FIR_MAX_TAPS; origin outside [0, ntap); a non-finite tap; transpose not 0 or 1.
+ * Needs no model.  Upload, one kernel, download; the traces and the taps live in grow-only device
+ * buffers of the context, freed with it.  All trace offsets are 64-bit.  alifmm_get_option:
+ * "trace_fir_upload_ms" (host -> device copies) and "trace_fir_kernel_ms" (the kernel) of the last
+ * call; "trace_fir_tile", the output samples a workgroup makes (a constant of the build: the results
+ * do not depend on it).  One GPU. */
+#define ALIFMM_FIR_MAX_TAPS 1024
+int alifmm_trace_fir(alifmm_ctx* ctx, int64_t ntrace, int nt, int ncomp, const double* in, int ntap, int tap_comp,
+                     const double* taps, int origin, int transpose, double* out);
+
+/* Pulse-aware least-squares imaging: alifmm_tfm_lsq with the pulse in the operator,
+ * min |P A x - d|^2 + damp^2 |x|^2 + smooth^2 |D x|^2 by CGLS from x = 0.
+ *   subgrid ... tol    as in alifmm_tfm_lsq
+ *   ntap, tap_comp, taps, origin
+ *                      the pulse, as in alifmm_trace_fir
+ *   image, resid, info8
+ *                      as in alifmm_tfm_lsq
+ * The contract is alifmm_tfm_lsq's, word for word, with P A in place of A and A^T P^T in place of
+ * A^T: A and A^T as there, P (alifmm_trace_fir) acting on each of the ntx nrx traces of nt samples.
+ *   r = d; s = A^T (P^T r); p = s; gamma_0 = gamma = |s|^2; gamma_0 == 0: stop (breakdown)
+ *   iteration it = 1, 2, ...:
+ *     q = P (A p); qq = |q|^2 + p . R(p); qq == 0: stop (breakdown; the iteration does not count)
+ *     alpha = gamma / qq; x += alpha p; r -= alpha q
+ *     s = A^T (P^T r) - R(x); gamma' = |s|^2; beta = gamma' / gamma; p = s + beta p; gamma = gamma'
+ *     gamma <= tol^2 gamma_0: stop (tol); it == max_iter: stop (max_iter)
+ * resid is the recurred d - P A x; info8 keeps its meaning, sqrt(gamma_0) being |A^T P^T d|.  P and
+ * P^T have a fixed order and add no new source of non-reproducibility; A sums with atomics as
+ * before, so a solve is reproducible to rounding only.
+ * ALIFMM_E_ARG with a message, the context staying usable and nothing written: every condition of
+ * alifmm_tfm_lsq; taps NULL; tap_comp not 1 or 2; tap_comp 2 with ncomp 1; ntap < 1 or
+ * ntap > ALIFMM_FIR_MAX_TAPS; origin outside [0, ntap); a non-finite tap.  A failed device
+ * allocation returns ALIFMM_E_HIP with the call's buffers freed.
+ * The vectors are alifmm_tfm_lsq's and one more of the data's size (three instead of two): A writes
+ * it and P reads it, P^T writes it and A^T reads it; with more than one slab it is what is zeroed
+ * every iteration.  The options and the "tfm_lsq_*" read-outs are alifmm_tfm_lsq's.  One GPU. */
+int alifmm_tfm_lsq_pulse(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx,
+                         const int32_t* rx_slot, const double* fmc, int nt, int ncomp, double t0, double fs,
+                         const float* pair_w, int iz0, int ix0, int niz, int nix, int step, double damp, double smooth,
+                         int max_iter, double tol, int ntap, int tap_comp, const double* taps, int origin, double* image,
+                         double* resid, double* info8);
+
 /* Travel-time sensitivities along rays: for every ray, the derivative of its time of flight in
  * every coarse cell it crosses (Fermat: to first order the path is fixed) — the rows of the
  * travel-time tomography Jacobian, and / or their weighted sums over the rays as three maps on the
