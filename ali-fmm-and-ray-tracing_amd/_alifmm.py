@@ -92,6 +92,8 @@ def _load():
                                     _p, _p, _p]),
             "alifmm_tfm_lsq_pulse": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _d, _d, _i,
                                           _d, _i, _i, _p, _i, _p, _p, _p]),
+            "alifmm_tfm_sparse": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _d, _d, _i, _d,
+                                       _i, _i, _p, _i, _d, _d, _i, _i, _p, _p, _p]),
             "alifmm_trace_fir": (_i, [_p, _l, _i, _i, _p, _i, _i, _p, _i, _i, _p]),
             "alifmm_ray_sens": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p]),
             "alifmm_sens_op_build": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
@@ -500,6 +502,56 @@ class Context:
                                                  _ptr(img), _ptr(res), _ptr(info)), "tfm_lsq")
         out = {"iterations": int(info[0]), "grad0": info[1], "grad": info[2], "rhs_norm": info[3], "res_norm": info[4],
                "reason": self.SOLVE_REASONS[int(info[5])]}
+        image = img.view(np.complex128)[..., 0] if cplx else img[..., 0]
+        if not resid:
+            return image, out
+        return image, out, (res.view(np.complex128)[..., 0] if cplx else res[..., 0])
+
+    def tfm_sparse(self, tx_slots, rx_slots, fmc, fs, t0=0.0, weights=None, window=None, step=1, subgrid=1, damp=0.0,
+                   smooth=0.0, max_iter=500, tol=1e-6, resid=False, pulse=None, pulse_origin=0, lam=None, lam_rel=None,
+                   lipschitz=0.0, power_iters=20, restart=True):
+        """Sparsity-regularised image of full-matrix-capture data over resident fields
+        (alifmm_tfm_sparse): the minimiser of ½ |P A x - fmc|² + ½ damp² |x|² + ½ smooth² |D x|² +
+        lam Σ_pixels |x_p| by FISTA with backtracking and gradient restart from x = 0.  A, P, D, damp
+        and smooth are tfm_lsq()'s; |x_p| is the modulus of a pixel (a complex pixel is one group,
+        its phase is not penalised).  The data and every vector of the iteration stay on the
+        device; one image comes back.  A sums with atomics, so two solves agree to rounding only.
+
+        tx_slots ... subgrid, damp, smooth, pulse, pulse_origin: as in tfm_lsq().  lam: the weight
+        of the ℓ1 term in the units of the gradient Aᵀ Pᵀ fmc; lam_rel: the same in units of
+        lam_max = max_p |(Aᵀ Pᵀ fmc)_p|, the smallest lam whose minimiser is 0 (the library takes
+        lam_max from its own first gradient; a negative lam means the same, as at the C level).
+        Exactly one of the two.  lipschitz: an estimate of
+        |BᵀB + R|₂, or 0 for power_iters rounds of the power method; it is doubled whenever a step
+        fails its descent test.  restart: gradient restart of the momentum.  The stop rule is
+        L |x⁺ - y| <= tol grad0.
+        Returns (image, info), or (image, info, resid) with resid=True (fmc - P A image, computed):
+        info = dict(iterations, grad0 = |Aᵀ Pᵀ fmc|, grad (the last L |x⁺ - y|), rhs_norm, res_norm,
+        reason ("tol", "max_iter" or "breakdown"), lam_max, lam, lipschitz (the final L),
+        backtracks, restarts, nnz (non-zero pixels))."""
+        if (lam is None) == (lam_rel is None):
+            raise ValueError("tfm_sparse: give exactly one of lam and lam_rel")
+        if lam_rel is not None and not float(lam_rel) >= 0:
+            raise ValueError("tfm_sparse: lam_rel %r is negative or not a number" % (lam_rel,))
+        step = int(step)
+        tx, rx, data, cplx, w, window = self._tfm_args("tfm_sparse", tx_slots, rx_slots, fmc, weights, window, step,
+                                                       subgrid, True)
+        iz0, ix0, niz, nix = window
+        nc = 2 if cplx else 1
+        img = np.zeros((max(niz, 0), max(nix, 0), nc))
+        res = np.zeros(data.shape + (nc,)) if resid else None
+        info = np.zeros(12)
+        taps = None if pulse is None else self._pulse_args("tfm_sparse", pulse, cplx)
+        # (a relative lam travels as its negative; -0.0 is the absolute 0, the same problem)
+        self._chk(lib().alifmm_tfm_sparse(
+            self._h, int(subgrid), len(tx), _ptr(tx), len(rx), _ptr(rx), _ptr(data), data.shape[2], nc, float(t0),
+            float(fs), _ptr(w), iz0, ix0, niz, nix, step, float(damp), float(smooth), int(max_iter), float(tol),
+            0 if taps is None else taps.shape[0], 1 if taps is None else taps.shape[1], _ptr(taps), int(pulse_origin),
+            float(lam) if lam is not None else -float(lam_rel), float(lipschitz), int(power_iters), int(bool(restart)),
+            _ptr(img), _ptr(res), _ptr(info)), "tfm_sparse")
+        out = {"iterations": int(info[0]), "grad0": info[1], "grad": info[2], "rhs_norm": info[3], "res_norm": info[4],
+               "reason": self.SOLVE_REASONS[int(info[5])], "lam_max": info[6], "lam": info[7], "lipschitz": info[8],
+               "backtracks": int(info[9]), "restarts": int(info[10]), "nnz": int(info[11])}
         image = img.view(np.complex128)[..., 0] if cplx else img[..., 0]
         if not resid:
             return image, out

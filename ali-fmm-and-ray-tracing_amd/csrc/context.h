@@ -268,6 +268,13 @@ struct alifmm_ctx {
   } tfm_lsq;
   double t_tfm_lsq_upload = 0, t_tfm_lsq_kernel = 0;  // last alifmm_tfm_lsq / alifmm_tfm_lsq_pulse (ms)
   int tfm_lsq_iters = 0;
+  // alifmm_tfm_sparse: grow-only device buffers (d, B x, B x⁺ and r: 4 x the data, and w with a pulse:
+  // 5 x; x, x⁺, y, g and t: 5 x the image; the window's pixel list, pair weights, slot pointer table,
+  // partial sums + scalars), freed with the context, or by a call whose allocation fails
+  TfmLsqBufs tfm_sparse;
+  double t_tfm_sparse_upload = 0, t_tfm_sparse_kernel = 0;  // last alifmm_tfm_sparse (ms)
+  int tfm_sparse_iters = 0, tfm_sparse_backtracks = 0;
+  double tfm_sparse_l0 = 0;  // the L its first iteration began with (given, or the power estimate)
   // alifmm_trace_fir: grow-only device buffers (the traces in and out, the taps; the taps also serve
   // alifmm_tfm_lsq_pulse), freed with the context
   struct FirBufs {

@@ -79,6 +79,7 @@ extern "C" int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   ctx->seed = {};
   ctx->tfm = {};
   ctx->tfm_lsq = {};
+  ctx->tfm_sparse = {};
   ctx->fir = {};
   ctx->tfm_model = {};
   ctx->skip = {};
@@ -198,6 +199,12 @@ extern "C" int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* valu
   else if (!strcmp(name, "tfm_lsq_upload_ms")) *value = ctx->t_tfm_lsq_upload;
   else if (!strcmp(name, "tfm_lsq_kernel_ms")) *value = ctx->t_tfm_lsq_kernel;
   else if (!strcmp(name, "tfm_lsq_iters")) *value = ctx->tfm_lsq_iters;
+  // last alifmm_tfm_sparse call: the same, the doublings of L, and the L its first iteration began with
+  else if (!strcmp(name, "tfm_sparse_upload_ms")) *value = ctx->t_tfm_sparse_upload;
+  else if (!strcmp(name, "tfm_sparse_kernel_ms")) *value = ctx->t_tfm_sparse_kernel;
+  else if (!strcmp(name, "tfm_sparse_iters")) *value = ctx->tfm_sparse_iters;
+  else if (!strcmp(name, "tfm_sparse_backtracks")) *value = ctx->tfm_sparse_backtracks;
+  else if (!strcmp(name, "tfm_sparse_l0")) *value = ctx->tfm_sparse_l0;
   // last alifmm_trace_fir call (ms): host -> device copies (host clock), the kernel (HIP events); the
   // outputs per workgroup of the kernel (a constant of the build)
   else if (!strcmp(name, "trace_fir_upload_ms")) *value = ctx->t_fir_upload;

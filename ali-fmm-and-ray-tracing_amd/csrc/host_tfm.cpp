@@ -2,7 +2,8 @@
 // alifmm_tfm_model (its transpose) and alifmm_tfm_lsq (the least-squares solve on both).  One front
 // half: the checks (tfm_check), the parameter blocks (tfm_params, tfm_model_params) and the
 // modelling kernel's launch plan (tfm_model_plan).  alifmm_tfm_lsq_pulse is the same solve with the
-// trace FIR (host_fir.cpp, trace_fir.hip) around the two products.
+// trace FIR (host_fir.cpp, trace_fir.hip) around the two products, and alifmm_tfm_sparse the
+// ℓ1-regularised solve (FISTA, tfm_sparse.hip) on the same two products (TfmOperator).
 #include <chrono>
 
 #include "host_internal.h"
@@ -274,6 +275,61 @@ extern "C" int alifmm_tfm_model(alifmm_ctx* ctx, int subgrid, int ntx, const int
   return ALIFMM_OK;
 }
 
+// What the solves over B = P A share on the device (F null: no pulse, B = A): the small buffers of
+// a call and their upload, and the two products.  With a pulse a data-sized vector `mid` lies
+// between the FIR and A (A writes it and P reads it, Pᵀ writes it and Aᵀ reads it).
+struct TfmOperator {
+  alifmm_ctx* ctx;
+  const TfmCall& C;
+  const TfmModelPlan& plan;
+  const FirTaps* F;
+  const double* const* tab = nullptr;
+  int64_t* pix = nullptr;
+  const float* w = nullptr;
+  double* mid = nullptr;
+
+  // the pixel list, the weights, the slot table and the taps into B's buffers (the copies before
+  // the caller's own time stamp ends)
+  hipError_t stage(alifmm_ctx::TfmLsqBufs& B, const std::vector<const double*>& t, const float* pair_w) {
+    hipError_t e = B.pix.grow(C.nwin());
+    if (e == hipSuccess && pair_w) e = B.w.grow(C.npair());
+    if (e == hipSuccess) e = B.tab.grow(t.size());
+    if (e == hipSuccess && F) e = ctx->fir.taps.grow((size_t)F->ntap * F->tap_comp);
+    if (e == hipSuccess && F)
+      e = hipMemcpy(ctx->fir.taps, F->taps, (size_t)F->ntap * F->tap_comp * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && pair_w) e = hipMemcpy(B.w, pair_w, C.npair() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(B.tab, t.data(), t.size() * sizeof(double*), hipMemcpyHostToDevice);
+    tab = B.tab;
+    pix = B.pix;
+    w = pair_w ? B.w.p : nullptr;
+    return e;
+  }
+  hipError_t pixels() const {
+    return af_launch_tfm_lsq_pix(C.iz0, C.ix0, C.step, C.fx, C.niz, C.nix, pix, ctx->stream);
+  }
+  // out = P in (transpose 0) or Pᵀ in (1) over the ntx nrx traces
+  hipError_t fir(const double* in, double* out, int transpose) const {
+    const af::TraceFirParams Q{in, out, ctx->fir.taps, (int64_t)C.npair(), C.nt, F->ntap, F->origin, transpose};
+    return af_launch_trace_fir(&Q, C.ncomp, F->tap_comp, ctx->stream);
+  }
+  // out = B refl
+  hipError_t forward(const double* refl, double* out) const {
+    double* const aq = F ? mid : out;  // what A writes
+    const af::TfmModelParams M = tfm_model_params(ctx, C, plan, tab, pix, C.nwin(), refl, w, aq);
+    // several slabs add into what A writes with atomics: zeroed every time
+    hipError_t e = plan.slabs > 1 ? hipMemsetAsync(aq, 0, C.ndata() * sizeof(double), ctx->stream) : hipSuccess;
+    if (e == hipSuccess) e = af_launch_tfm_model(&M, ctx->stream);
+    if (e == hipSuccess && F) e = fir(aq, out, 0);
+    return e;
+  }
+  // t = Bᵀ r
+  hipError_t adjoint(const double* r, double* t) const {
+    hipError_t e = F ? fir(r, mid, 1) : hipSuccess;
+    const af::TfmParams T = tfm_params(C, tab, nullptr, F ? mid : r, w, t);
+    return e == hipSuccess ? af_launch_tfm_f64(&T, ctx->tfm_chunk, ctx->stream) : e;
+  }
+};
+
 // The device half of alifmm_tfm_lsq (F null) and of alifmm_tfm_lsq_pulse (F: the pulse), after the
 // checks: hipSuccess or the first error (the caller frees the call's buffers on one).  With a pulse
 // the operator is P A: a third data-sized vector w lies between the FIR and the two products
@@ -293,10 +349,6 @@ static hipError_t tfm_lsq_run(alifmm_ctx* ctx, const std::vector<const double*>&
   LSQ(B.data.grow((F ? 3 : 2) * nd));
   LSQ(B.img.grow(4 * ni));
   LSQ(B.small.grow((size_t)af::kSolveMaxParts + af::kSolScalars));
-  LSQ(B.pix.grow(npix));
-  if (pair_w) LSQ(B.w.grow(C.npair()));
-  LSQ(B.tab.grow(tab.size()));
-  if (F) LSQ(ctx->fir.taps.grow((size_t)F->ntap * F->tap_comp));
   af::SolveVecs V;
   V.x = B.img;
   V.p = B.img + ni;
@@ -309,13 +361,11 @@ static hipError_t tfm_lsq_run(alifmm_ctx* ctx, const std::vector<const double*>&
   V.scal = B.small + af::kSolveMaxParts;
   V.damp2 = damp * damp;
   V.smooth2 = smooth * smooth;
-  double* const aq = F ? B.data + 2 * nd : V.q;        // what A writes: q, or w with a pulse
-  const double* const atr = F ? B.data + 2 * nd : V.r;  // what Aᵀ reads: r, or w = Pᵀ r
+  TfmOperator Op{ctx, C, plan, F};
+  Op.mid = F ? B.data + 2 * nd : nullptr;
   const auto c0 = std::chrono::steady_clock::now();
   LSQ(hipMemcpy(V.r, fmc, nd * sizeof(double), hipMemcpyHostToDevice));
-  if (F) LSQ(hipMemcpy(ctx->fir.taps, F->taps, (size_t)F->ntap * F->tap_comp * sizeof(double), hipMemcpyHostToDevice));
-  if (pair_w) LSQ(hipMemcpy(B.w, pair_w, C.npair() * sizeof(float), hipMemcpyHostToDevice));
-  LSQ(hipMemcpy(B.tab, tab.data(), tab.size() * sizeof(double*), hipMemcpyHostToDevice));
+  LSQ(Op.stage(B, tab, pair_w));
   ctx->t_tfm_lsq_upload = ms_since(c0);
   af::TfmLsqDims G;
   G.niz = C.niz;
@@ -323,32 +373,15 @@ static hipError_t tfm_lsq_run(alifmm_ctx* ctx, const std::vector<const double*>&
   G.nc = C.ncomp;
   G.nimg = (int64_t)ni;
   G.ndata = (int64_t)nd;
-  const float* w = pair_w ? B.w.p : nullptr;
-  const af::TfmParams T = tfm_params(C, B.tab, nullptr, atr, w, V.t);                           // t = Aᵀ r
-  const af::TfmModelParams M = tfm_model_params(ctx, C, plan, B.tab, B.pix, npix, V.p, w, aq);  // q = A p
   hipStream_t st = ctx->stream;
-  const int chunk = ctx->tfm_chunk;
-  // q = P w (transpose 0) or w = Pᵀ r (1) over the ntx nrx traces; nothing without a pulse
-  const auto fir = [&](int transpose) {
-    if (!F) return hipSuccess;
-    const af::TraceFirParams Q{transpose ? V.r : aq, transpose ? aq : V.q, ctx->fir.taps, (int64_t)C.npair(),
-                               C.nt, F->ntap, F->origin, transpose};
-    return af_launch_trace_fir(&Q, C.ncomp, F->tap_comp, st);
-  };
-  const auto form_t = [&] {
-    hipError_t e = fir(1);
-    return e == hipSuccess ? af_launch_tfm_f64(&T, chunk, st) : e;
-  };
+  const auto form_t = [&] { return Op.adjoint(V.r, V.t); };  // t = Aᵀ r, with a pulse Aᵀ Pᵀ r
   LSQ(hipEventRecord(ctx->ev[0], st));
-  LSQ(af_launch_tfm_lsq_pix(C.iz0, C.ix0, C.step, C.fx, C.niz, C.nix, B.pix, st));
+  LSQ(Op.pixels());
   LSQ(cgls_run(
       V, ni, nd, st, ctx->ev[0], ctx->ev[1], max_iter, tol, form_t,
       [&] { return af_launch_tfm_lsq_grad(&G, &V, 1, st); },  // x = 0: s = Aᵀ d, p = s, gamma_0 = |s|²
       [&] {
-        // several slabs add into q (with a pulse: w) with atomics: zeroed every iteration
-        hipError_t e = plan.slabs > 1 ? hipMemsetAsync(aq, 0, nd * sizeof(double), st) : hipSuccess;
-        if (e == hipSuccess) e = af_launch_tfm_model(&M, st);
-        if (e == hipSuccess) e = fir(0);
+        hipError_t e = Op.forward(V.p, V.q);  // q = A p, with a pulse P A p
         if (e == hipSuccess) e = af_launch_tfm_lsq_step(&G, &V, st);
         if (e == hipSuccess) e = form_t();
         if (e == hipSuccess) e = af_launch_tfm_lsq_grad(&G, &V, 0, st);
@@ -408,4 +441,197 @@ extern "C" int alifmm_tfm_lsq_pulse(alifmm_ctx* ctx, int subgrid, int ntx, const
   return tfm_lsq_impl(ctx, "tfm_lsq_pulse", subgrid, tx_slot, rx_slot, fmc, pair_w,
                       {ntx, nrx, nt, ncomp, t0, fs, iz0, ix0, niz, nix, step, 0}, &F, damp, smooth, max_iter, tol, image,
                       resid, info8);
+}
+
+// ---- alifmm_tfm_sparse ----
+
+// what a sparse solve reports beside the image (info12)
+struct SparseResult {
+  int iters = 0, reason = 1, backtracks = 0, restarts = 0;
+  double g0 = 0, gk = 0, rhs = 0, res = 0, lam_max = 0, lam = 0, L = 0, nnz = 0;
+  void pack(double* info12) const {
+    const double info[12] = {(double)iters, g0, gk, rhs, res, (double)reason, lam_max, lam, L, (double)backtracks,
+                             (double)restarts, nnz};
+    std::copy(info, info + 12, info12);
+  }
+};
+
+// The device half of alifmm_tfm_sparse after the checks (F null: no pulse): FISTA with backtracking
+// and gradient restart, the iteration of include/alifmm.h line for line.  hipSuccess or the first
+// error (the caller frees the call's buffers on one).  x and x⁺, B x and B x⁺ swap by pointer when a
+// trial is accepted; B y is never formed.
+static hipError_t tfm_sparse_run(alifmm_ctx* ctx, const std::vector<const double*>& tab, const TfmCall& C,
+                                 const TfmModelPlan& plan, const FirTaps* F, const double* fmc, const float* pair_w,
+                                 double damp, double smooth, int max_iter, double tol, double lam, double lipschitz,
+                                 int power_iters, int restart, double* image, double* resid, SparseResult* R) {
+#define SP(call)                     \
+  do {                               \
+    hipError_t e_ = (call);          \
+    if (e_ != hipSuccess) return e_; \
+  } while (0)
+  const size_t npix = C.nwin(), nd = C.ndata(), ni = npix * C.ncomp;
+  SP(hipSetDevice(ctx->device));
+  alifmm_ctx::TfmLsqBufs& B = ctx->tfm_sparse;
+  SP(B.data.grow((F ? 5 : 4) * nd));
+  SP(B.img.grow(5 * ni));
+  SP(B.small.grow((size_t)af::kSpPartArrays * af::kSolveMaxParts + af::kSpScalars + af::kSolScalars));
+  af::SparseVecs V;
+  V.x = B.img;
+  V.y = B.img + ni;  // (y follows x: both zeroed at once)
+  V.xn = B.img + 2 * ni;
+  V.g = B.img + 3 * ni;
+  V.t = B.img + 4 * ni;
+  V.d = B.data;
+  V.bx = B.data + nd;
+  V.bxn = B.data + 2 * nd;
+  V.r = B.data + 3 * nd;
+  V.parts = B.small;
+  V.scal = B.small + (size_t)af::kSpPartArrays * af::kSolveMaxParts;
+  V.damp2 = damp * damp;
+  V.smooth2 = smooth * smooth;
+  af::SolveVecs N = {};  // what af_launch_solve_norm takes: the partials and a scalar block of its own
+  N.parts = V.parts;
+  N.scal = V.scal + af::kSpScalars;
+  TfmOperator Op{ctx, C, plan, F};
+  Op.mid = F ? B.data + 4 * nd : nullptr;
+  const auto c0 = std::chrono::steady_clock::now();
+  SP(hipMemcpy(V.d, fmc, nd * sizeof(double), hipMemcpyHostToDevice));
+  SP(Op.stage(B, tab, pair_w));
+  ctx->t_tfm_sparse_upload = ms_since(c0);
+  af::TfmLsqDims G;
+  G.niz = C.niz;
+  G.nix = C.nix;
+  G.nc = C.ncomp;
+  G.nimg = (int64_t)ni;
+  G.ndata = (int64_t)nd;
+  hipStream_t st = ctx->stream;
+  // n scalars of the device's from `which` on (at most 32 bytes, one copy) after the work queued so far
+  const auto scalars = [&](int which, int n, double* v) {
+    hipError_t e = hipMemcpyAsync(v, V.scal + which, (size_t)n * 8, hipMemcpyDeviceToHost, st);
+    return e == hipSuccess ? hipStreamSynchronize(st) : e;
+  };
+  SP(hipEventRecord(ctx->ev[0], st));
+  SP(Op.pixels());
+  SP(hipMemsetAsync(V.x, 0, 2 * ni * sizeof(double), st));  // x = y = 0
+  SP(hipMemsetAsync(V.bx, 0, nd * sizeof(double), st));     // B x = 0
+  SP(hipMemsetAsync(V.scal, 0, (af::kSpScalars + af::kSolScalars) * sizeof(double), st));
+  SP(af_launch_solve_norm(V.d, (long)nd, &N, st));  // |d|²
+  SP(Op.adjoint(V.d, V.t));                         // t = Bᵀ d
+  SP(af_launch_tfm_sparse_start(&G, &V, N.scal + af::kSolNorm, st));
+  double s4[4];
+  SP(scalars(af::kSpG0, 3, s4));  // |g0|², lam_max, |d|²
+  R->g0 = sqrt(s4[0]);
+  R->lam_max = s4[1];
+  R->rhs = sqrt(s4[2]);
+  R->lam = lam < 0 ? -lam * R->lam_max : lam;
+  double L = lipschitz;
+  bool go = R->g0 != 0.0;
+  if (go && !(lipschitz > 0)) {  // the power estimate: v = g0 / |g0|; w = Bᵀ B v + R(v), est = |w|, v = w / |w|
+    for (int k = 0; k < power_iters; k++) {
+      SP(af_launch_tfm_sparse_power_scale(&G, &V, st));
+      SP(Op.forward(V.xn, V.bxn));
+      SP(Op.adjoint(V.bxn, V.t));
+      SP(af_launch_tfm_sparse_power(&G, &V, st));
+    }
+    SP(scalars(af::kSpEst, 1, &L));
+    go = std::isfinite(L) && L > 0;
+  }
+  ctx->tfm_sparse_l0 = go ? L : 0.0;
+  R->reason = go ? 1 : 2;
+  double theta = 1.0;
+  int doublings = 0;
+  for (int k = 1; go && k <= max_iter; k++) {
+    // (g and fy belong to y: the start left them for y = 0, the end of an iteration for the next)
+    for (;;) {
+      const double step = 1.0 / L, tau = R->lam * step;
+      SP(af_launch_tfm_sparse_prox(&G, &V, step, tau, st));
+      SP(Op.forward(V.xn, V.bxn));
+      SP(af_launch_tfm_sparse_trial(&G, &V, L, st));
+      SP(scalars(af::kSpOut, 4, s4));  // the one read of a trial: f⁺, Q + slack, |x⁺ - y|², the restart dot
+      if (s4[0] <= s4[1]) break;
+      if (++doublings > af::kSpMaxDoublings) {
+        go = false;
+        break;
+      }
+      L = 2 * L;
+      R->backtracks++;
+    }
+    if (!go) {
+      R->reason = 2;
+      break;
+    }
+    R->gk = L * sqrt(s4[2]);
+    R->iters = k;
+    std::swap(V.x, V.xn);  // x⁺ is the iterate, the old iterate the next trial's room
+    std::swap(V.bx, V.bxn);
+    if (restart && s4[3] > 0) theta = 1.0, R->restarts++;
+    const double theta1 = (1.0 + sqrt(1.0 + 4.0 * theta * theta)) / 2.0, beta = (theta - 1.0) / theta1;
+    theta = theta1;
+    if (R->gk <= tol * R->g0) {
+      R->reason = 0;
+      break;
+    }
+    if (k == max_iter) break;  // (the momentum step of a last iteration would serve nothing)
+    // (after the swap x is x⁺ and xn the iterate before it)
+    af::SparseVecs W = V;
+    W.xn = V.x, W.x = V.xn, W.bxn = V.bx, W.bx = V.bxn;
+    SP(af_launch_tfm_sparse_momentum(&G, &W, beta, st));
+    SP(Op.adjoint(V.r, V.t));
+    SP(af_launch_tfm_sparse_grad(&G, &V, st));
+  }
+  R->L = L;
+  SP(af_launch_tfm_sparse_final(&G, &V, st));  // r = d - B x of the returned x, computed, and its non-zero pixels
+  SP(scalars(af::kSpRes, 2, s4));
+  R->res = sqrt(s4[0]);
+  R->nnz = s4[1];
+  SP(hipEventRecord(ctx->ev[1], st));
+  SP(hipStreamSynchronize(st));
+  float t = 0;
+  SP(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
+  ctx->t_tfm_sparse_kernel = t;
+  ctx->tfm_sparse_iters = R->iters;
+  ctx->tfm_sparse_backtracks = R->backtracks;
+  SP(hipMemcpy(image, V.x, ni * sizeof(double), hipMemcpyDeviceToHost));
+  if (resid) SP(hipMemcpy(resid, V.r, nd * sizeof(double), hipMemcpyDeviceToHost));
+  return hipSuccess;
+#undef SP
+}
+
+extern "C" int alifmm_tfm_sparse(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx,
+                                 const int32_t* rx_slot, const double* fmc, int nt, int ncomp, double t0, double fs,
+                                 const float* pair_w, int iz0, int ix0, int niz, int nix, int step, double damp,
+                                 double smooth, int max_iter, double tol, int ntap, int tap_comp, const double* taps,
+                                 int origin, double lam, double lipschitz, int power_iters, int restart, double* image,
+                                 double* resid, double* info12) {
+  if (!ctx) return ALIFMM_E_ARG;
+  const char* what = "tfm_sparse";
+  TfmCall C{ntx, nrx, nt, ncomp, t0, fs, iz0, ix0, niz, nix, step, 0};
+  std::vector<const double*> tab;
+  if (int rc = tfm_check(ctx, what, subgrid, tx_slot, rx_slot, fmc, image, C, tab)) return rc;
+  if (!info12) return fail(ctx, ALIFMM_E_ARG, "%s: info12 is NULL", what);
+  if (int rc = cgls_check(ctx, what, damp, smooth, max_iter, tol)) return rc;
+  const bool pulse = ntap != 0 || taps != nullptr;  // ntap 0 and taps NULL: no pulse
+  const FirTaps F{ntap, tap_comp, taps, origin};
+  if (pulse)
+    if (int rc = fir_check_taps(ctx, what, C.ncomp, F)) return rc;
+  if (!std::isfinite(lam)) return fail(ctx, ALIFMM_E_ARG, "%s: lam %g", what, lam);
+  if (!(lipschitz >= 0) || !std::isfinite(lipschitz)) return fail(ctx, ALIFMM_E_ARG, "%s: lipschitz %g", what, lipschitz);
+  if (!(lipschitz > 0) && power_iters < 1)
+    return fail(ctx, ALIFMM_E_ARG, "%s: power_iters %d without a lipschitz constant", what, power_iters);
+  if (restart != 0 && restart != 1) return fail(ctx, ALIFMM_E_ARG, "%s: restart %d is not 0 or 1", what, restart);
+  const size_t nd = C.ndata();
+  for (size_t k = 0; k < nd; k++)
+    if (!std::isfinite(fmc[k])) return fail(ctx, ALIFMM_E_ARG, "%s: fmc[%zu] is not finite", what, k);
+  TfmModelPlan plan;
+  if (int rc = tfm_model_plan(ctx, what, C, C.nwin(), &plan)) return rc;
+  SparseResult R;
+  const hipError_t e = tfm_sparse_run(ctx, tab, C, plan, pulse ? &F : nullptr, fmc, pair_w, damp, smooth, max_iter, tol,
+                                      lam, lipschitz, power_iters, restart, image, resid, &R);
+  if (e != hipSuccess) {  // (out of memory, for one): the call's buffers go
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->tfm_sparse = {};
+    return fail(ctx, ALIFMM_E_HIP, "%s: %s", what, hipGetErrorString(e));
+  }
+  R.pack(info12);
+  return ALIFMM_OK;
 }

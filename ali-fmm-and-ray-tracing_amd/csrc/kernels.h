@@ -7,6 +7,7 @@
 #include "tfm_coh_term.h"  // af::TfmCohParams: the same of the coherence-weighted TFM kernel (tfm_coh.hip)
 #include "tfm_model_term.h"  // af::TfmModelParams: the same of the FMC modelling kernel (tfm_model.hip)
 #include "tfm_solve_ops.h"  // af::TfmLsqDims: the vectors' shapes of the least-squares imaging solve (tfm_solve.hip)
+#include "tfm_sparse_ops.h"  // the scalars and partial arrays of sparsity-regularised imaging (tfm_sparse.hip)
 #include "trace_fir_term.h"  // the trace FIR's sum and tile walk (trace_fir.hip)
 
 namespace af {
@@ -211,6 +212,15 @@ struct SolveVecs {
   double damp2, smooth2;
 };
 
+// device vectors and scalars of alifmm_tfm_sparse (tfm_sparse.hip)
+struct SparseVecs {
+  double *x, *xn, *y, *g, *t;  // [nimg]: the iterate, the trial x⁺, the momentum point, the gradient at y, t = Bᵀ r
+  double *d, *bx, *bxn, *r;    // [ndata]: the data, B x, B x⁺, r = B y - d
+  double* parts;               // [kSpPartArrays][kSolveMaxParts] partial sums
+  double* scal;                // [kSpScalars] (tfm_sparse_ops.h)
+  double damp2, smooth2;
+};
+
 // the trace FIR (trace_fir.hip): out = P in (transpose 0) or Pᵀ in (1) over ntrace traces of nt
 // samples; in and out distinct device vectors [ntrace][nt][ncomp], taps [ntap][tap_comp] on the device
 struct TraceFirParams {
@@ -293,6 +303,17 @@ hipError_t af_launch_solve_scalar(int what, const double* parts, int nparts, dou
 hipError_t af_launch_tfm_lsq_pix(int iz0, int ix0, int step, int fnx, int niz, int nix, int64_t* pix, hipStream_t stream);
 hipError_t af_launch_tfm_lsq_step(const af::TfmLsqDims* G, const af::SolveVecs* V, hipStream_t stream);
 hipError_t af_launch_tfm_lsq_grad(const af::TfmLsqDims* G, const af::SolveVecs* V, int start, hipStream_t stream);
+// sparsity-regularised imaging (tfm_sparse.hip): the fused passes between the products of a FISTA
+// iteration; each sums in two stages and leaves its scalars in V->scal (tfm_sparse_ops.h)
+hipError_t af_launch_tfm_sparse_start(const af::TfmLsqDims* G, const af::SparseVecs* V, const double* rr, hipStream_t stream);
+hipError_t af_launch_tfm_sparse_power_scale(const af::TfmLsqDims* G, const af::SparseVecs* V, hipStream_t stream);
+hipError_t af_launch_tfm_sparse_power(const af::TfmLsqDims* G, const af::SparseVecs* V, hipStream_t stream);
+hipError_t af_launch_tfm_sparse_grad(const af::TfmLsqDims* G, const af::SparseVecs* V, hipStream_t stream);
+hipError_t af_launch_tfm_sparse_prox(const af::TfmLsqDims* G, const af::SparseVecs* V, double step, double tau,
+                                     hipStream_t stream);
+hipError_t af_launch_tfm_sparse_trial(const af::TfmLsqDims* G, const af::SparseVecs* V, double L, hipStream_t stream);
+hipError_t af_launch_tfm_sparse_momentum(const af::TfmLsqDims* G, const af::SparseVecs* V, double beta, hipStream_t stream);
+hipError_t af_launch_tfm_sparse_final(const af::TfmLsqDims* G, const af::SparseVecs* V, hipStream_t stream);
 // the trace FIR and its transpose (trace_fir.hip; the sum: trace_fir_term.h); ncomp 1 or 2, tap_comp 1 or
 // 2 (2: ncomp 2), 1 <= ntap <= af::kFirMaxTaps, 0 <= origin < ntap.  af_trace_fir_tile: outputs per workgroup
 hipError_t af_launch_trace_fir(const af::TraceFirParams* P, int ncomp, int tap_comp, hipStream_t stream);

@@ -542,6 +542,72 @@ int alifmm_tfm_lsq_pulse(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* t
                          int max_iter, double tol, int ntap, int tap_comp, const double* taps, int origin, double* image,
                          double* resid, double* info8);
 
+/* Sparsity-regularised imaging: the minimiser of
+ *   F(x) = 1/2 |P A x - d|^2 + 1/2 damp^2 |x|^2 + 1/2 smooth^2 |D x|^2 + lam sum over pixels p of |x_p|
+ * by FISTA with backtracking and gradient restart from x = 0, everything resident on the device.
+ *   subgrid ... tol    as in alifmm_tfm_lsq_pulse (A, D, damp, smooth, the slots, window, step, t0,
+ *                      fs, weights, ncomp)
+ *   ntap, tap_comp, taps, origin
+ *                      the pulse, as in alifmm_trace_fir; ntap 0 with taps NULL: no pulse, P = I
+ *   lam                the weight of the l1 term, in the units of the gradient A^T P^T d (note the 1/2);
+ *                      negative: -lam is relative to lam_max (below), lam = -lam * lam_max
+ *   lipschitz          L, an estimate of |B^T B + R|_2; 0: the power estimate below
+ *   power_iters        rounds of the power estimate (lipschitz 0 only)
+ *   restart            1: gradient restart, 0: none
+ *   image              x, float64 [niz][nix][ncomp]: the last accepted x+, never y
+ *   resid (nullable)   d - P A x of the returned x, computed from it, not recurred; the shape of fmc
+ *   info12             iterations (accepted), G0 = |g0|, the last Gk, |d|, |d - B x|, the stop's reason
+ *                      (0 tol, 1 max_iter, 2 breakdown), lam_max, the lam used, the final L, backtracks,
+ *                      restarts, the non-zero pixels of x
+ * |x_p| is the modulus of pixel p over its components: |x| for ncomp 1, sqrt(re^2 + im^2) for ncomp 2
+ * (a complex pixel is one group; its phase is not penalised).  lam_max = max_p |(A^T P^T d)_p| is the
+ * smallest lam for which x = 0 is the minimiser.  With B = P A, R(v) = damp^2 v + smooth^2 D^T D v and
+ * f(v) = 1/2 |B v - d|^2 + 1/2 v . R(v), all in float64, no contraction, sqrt and / correctly rounded:
+ *   g0 = B^T d; G0 = |g0|; lam_max = max_p |g0_p|; G0 == 0: stop (breakdown), x = 0
+ *   L = lipschitz > 0 ? lipschitz : the power estimate: v = g0 / |g0|; power_iters times
+ *       w = B^T (B v) + R(v), est = |w|, v = w / est; L = est (not finite or 0: stop, breakdown)
+ *   x = y = 0; B x = 0; theta = 1; g = -g0; fy = 1/2 |d|^2
+ *   iteration k = 1, 2, ...:            (g = B^T r + R(y) with r = B y - d, fy = 1/2 |r|^2 + 1/2 y . R(y))
+ *     repeat:
+ *       step = 1 / L; tau = lam * step
+ *       per pixel: z_c = y_c - step * g_c; m = |z|;
+ *                  m > tau: fac = (m - tau) / m, x+_c = z_c * fac; else x+_c = +0.0
+ *       B x+ by the two kernels; f+ = 1/2 |B x+ - d|^2 + 1/2 x+ . R(x+)
+ *       Q = (fy + g . (x+ - y)) + (1/2 L) |x+ - y|^2
+ *       f+ <= Q + 2^-40 fy: accept; else L = 2 L, backtracks += 1
+ *       (more than 60 doublings in one call: stop, breakdown; the image is the last accepted x+)
+ *     Gk = L |x+ - y|                              (the norm of the gradient mapping)
+ *     restart != 0 and (y - x+) . (x+ - x) > 0: theta = 1, restarts += 1
+ *     theta+ = (1 + sqrt(1 + 4 theta^2)) / 2; beta = (theta - 1) / theta+; theta = theta+
+ *     Gk <= tol G0: stop (tol); k == max_iter: stop (max_iter)
+ *     y = x+ + beta (x+ - x); r = (B x+ + beta (B x+ - B x)) - d; x = x+; B x = B x+
+ *     fy and g for the new y
+ * B y is never computed: one A and one A^T (and the two FIR passes) run per accepted iteration, as in
+ * a CGLS iteration, and one more A (and P) per rejected trial.  2^-40 is a constant of the contract: it
+ * keeps the rounding of f+ and Q from doubling L once x+ is y to rounding.  The power estimate is a
+ * lower bound of the true constant, which is why the backtracking is not optional.  The host reads
+ * 32 bytes in one copy per trial (f+, Q + 2^-40 fy, |x+ - y|^2, the restart's dot product), 24 at the
+ * start, 8 after the power estimate and 16 at the end.  Every sum is a two-stage sum whose partial
+ * sums depend on the vector's length alone (the sums of one pass side by side), lam_max is a maximum
+ * and does not depend on an order, A^T and P have a fixed order; A sums with atomics, so a solve is
+ * reproducible to rounding only, NOT to the bit, exactly as alifmm_tfm_lsq.
+ * ALIFMM_E_ARG with a message, the context staying usable and nothing written: every condition of
+ * alifmm_tfm_lsq_pulse (the taps' only with a pulse); lam not finite; lipschitz negative or not
+ * finite; power_iters < 1 with lipschitz 0; restart not 0 or 1; info12 NULL.  A failed device
+ * allocation returns ALIFMM_E_HIP with the call's buffers freed.  The fields are not modified.
+ * The vectors live in grow-only device buffers of the context, freed with it: four of the data's size
+ * (d, B x, B x+, r; a fifth between P and A with a pulse) and five of the image's (x, x+, y, g and
+ * t = B^T r), and the pixel list.  alifmm_get_option: "tfm_sparse_upload_ms", "tfm_sparse_kernel_ms"
+ * (device time of the whole solve), "tfm_sparse_iters", "tfm_sparse_backtracks" and "tfm_sparse_l0"
+ * (the L the first iteration began with: lipschitz, or the power estimate) of the last call.
+ * "tfm_chunk" and the "tfm_model_*" options apply as in alifmm_tfm_lsq (with more than one slab what A
+ * writes is zeroed every time).  One GPU. */
+int alifmm_tfm_sparse(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot, int nrx, const int32_t* rx_slot,
+                      const double* fmc, int nt, int ncomp, double t0, double fs, const float* pair_w, int iz0, int ix0,
+                      int niz, int nix, int step, double damp, double smooth, int max_iter, double tol, int ntap,
+                      int tap_comp, const double* taps, int origin, double lam, double lipschitz, int power_iters,
+                      int restart, double* image, double* resid, double* info12);
+
 /* Travel-time sensitivities along rays: for every ray, the derivative of its time of flight in
  * every coarse cell it crosses (Fermat: to first order the path is fixed) — the rows of the
  * travel-time tomography Jacobian, and / or their weighted sums over the rays as three maps on the
