@@ -103,6 +103,7 @@ def _load():
             "alifmm_time_between_points": (_i, [_p, _i, _p, _p, _p, _p, _i, _p]),
             "alifmm_local_ops": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i,
                                       _p]),
+            "alifmm_cr_math": (_i, [_p, _i, _i, _l, _p, _p, _p]),
             "alifmm_fouds18_band": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
             "alifmm_comm_unique_id": (_i, [_p]),
             "alifmm_comm_init_rank": (_i, [_p, _i, _i, _p, _p]),
@@ -886,6 +887,23 @@ class Context:
         self._chk(lib().alifmm_local_ops(self._h, int(op), n, pz, px, _ptr(ttn), _ptr(nsts), *[_ptr(a) for a in args],
                                          _ptr(cst), _ptr(tab), tab.shape[1], _ptr(out)), "local_ops")
         return out
+
+    CR_FN = {"atan": 0, "sin": 1, "cos": 2, "tan": 3, "sincos": 4}
+
+    def cr_math(self, fn, x, lds_tables=False):
+        """The device's correctly rounded atan / sin / cos / tan / sincos (csrc/cr_math.h) of every
+        element of x (alifmm_cr_math); fn: a name of CR_FN or its number.  One array of x's shape,
+        a (sin, cos) pair for sincos.  lds_tables: read the tables from LDS, as the solver kernels do."""
+        if isinstance(fn, str):
+            if fn not in self.CR_FN:
+                raise AlifmmError("cr_math: unknown function %r (one of %s)" % (fn, ", ".join(self.CR_FN)))
+            fn = self.CR_FN[fn]
+        x = _c64(x)
+        out = np.empty_like(x)
+        out2 = np.empty_like(x) if fn == 4 else None
+        self._chk(lib().alifmm_cr_math(self._h, int(fn), int(lds_tables), x.size, _ptr(x), _ptr(out), _ptr(out2)),
+                  "cr_math")
+        return (out, out2) if fn == 4 else out
 
     def fouds18_band(self, ttn, nsts, iz, ix, dnx, dnz, nnz_arg, nnx_arg, mz, mx, quant=0):
         """fouds18_A() as the band kernel evaluates it: material of resident-model cell (mz, mx)

@@ -103,9 +103,11 @@ CR_COLD double atan_accurate(double x) {
     const double h = 1.0 / a;
     u = {h, fma(-h, a, 1.0) / a};
   }
-  const int k = (int)(u.h * 128.0 + 0.5);
+  // k = 0 below 2^-8: u.h * 128 + 0.5 rounds up to 1 at the double just below 2^-8, where
+  // u.h < c/2 and u.h - c would not be exact
+  const int k = u.h < 0x1p-8 ? 0 : (int)(u.h * 128.0 + 0.5);
   const double c = k * (1.0 / 128);
-  const dd n = two_sum(u.h - c, u.l);  // u.h - c exact (Sterbenz: c/2 <= u.h <= 2c for k >= 1)
+  const dd n = two_sum(u.h - c, u.l);  // u.h - c exact (k = 0: c = 0; k >= 1: Sterbenz, c/2 <= u.h <= 2c)
   dd p = two_prod(u.h, c);
   p.l += u.l * c;
   dd d = two_sum(1.0, p.h);
@@ -162,9 +164,10 @@ CR_HD double atan(double x) {
     uh = 1.0 / a;
     ul = fma(-uh, a, 1.0) * uh;
   }
-  const int k = (int)(uh * 128.0 + 0.5);
+  // k = 0 below 2^-8: uh * 128 + 0.5 rounds up to 1 at the double just below 2^-8, where uh < c/2
+  const int k = uh < 0x1p-8 ? 0 : (int)(uh * 128.0 + 0.5);
   const double c = k * (1.0 / 128);
-  const double nh = uh - c;  // exact (Sterbenz)
+  const double nh = uh - c;  // exact (k = 0: c = 0; k >= 1: uh >= 2^-8 >= c/2 and uh <= 2c, Sterbenz)
   const double ph = uh * c, pl = fma(uh, c, -ph) + ul * c;
   const double dh = 1.0 + ph, dl = ((1.0 - dh) + ph) + pl;  // 1 >= |ph|
   const double th = nh / dh;

@@ -1,5 +1,6 @@
 // host_ops.cpp — the module-level operators on the device: time_between_points, the local
-// operators of a batch of patches (local_ops) and the band kernel's fouds18 fallback (fouds18_band).
+// operators of a batch of patches (local_ops), the band kernel's fouds18 fallback (fouds18_band) and
+// the correctly rounded trigonometric functions themselves (cr_math).
 #include <cstring>
 
 #include "host_internal.h"
@@ -20,6 +21,30 @@ extern "C" int alifmm_time_between_points(alifmm_ctx* ctx, int n, const double* 
   if (e == hipSuccess) e = hipMemcpy(out, d + 4 * (size_t)n, 8 * (size_t)n, hipMemcpyDeviceToHost);
   dfree(d);
   if (e != hipSuccess) return fail(ctx, ALIFMM_E_HIP, "time_between_points: %s", hipGetErrorString(e));
+  return ALIFMM_OK;
+}
+
+extern "C" int alifmm_cr_math(alifmm_ctx* ctx, int fn, int lds_tables, int64_t n, const double* x, double* out,
+                              double* out2) {
+  if (!ctx) return ALIFMM_E_ARG;
+  if (fn < 0 || fn > 4) return fail(ctx, ALIFMM_E_ARG, "cr_math: fn %d (0 atan, 1 sin, 2 cos, 3 tan, 4 sincos)", fn);
+  if (lds_tables != 0 && lds_tables != 1) return fail(ctx, ALIFMM_E_ARG, "cr_math: lds_tables %d (0 or 1)", lds_tables);
+  if (n < 0) return fail(ctx, ALIFMM_E_ARG, "cr_math: n %lld", (long long)n);
+  if (n == 0) return ALIFMM_OK;
+  if (!x || !out || (fn == 4 && !out2)) return fail(ctx, ALIFMM_E_ARG, "cr_math: null %s", !x ? "x" : !out ? "out" : "out2");
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t m = (size_t)n, nout = fn == 4 ? 2 : 1;
+  double* d = nullptr;  // [x | out | out2]
+  HIPCHK(dalloc(&d, (1 + nout) * m));
+  hipError_t e = hipMemcpy(d, x, 8 * m, hipMemcpyHostToDevice);
+  double* d2 = fn == 4 ? d + 2 * m : nullptr;
+  if (e == hipSuccess)
+    e = lds_tables ? af_launch_cr_eval_lds(fn, n, d, d + m, d2, ctx->stream) : af_launch_cr_eval(fn, n, d, d + m, d2, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(out, d + m, 8 * m, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && fn == 4) e = hipMemcpy(out2, d2, 8 * m, hipMemcpyDeviceToHost);
+  dfree(d);
+  if (e != hipSuccess) return fail(ctx, ALIFMM_E_HIP, "cr_math: %s", hipGetErrorString(e));
   return ALIFMM_OK;
 }
 

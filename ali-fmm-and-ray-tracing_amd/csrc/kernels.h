@@ -264,6 +264,10 @@ hipError_t af_launch_skip_pick(const double* const* fld, int nfld, const int* w_
 hipError_t af_launch_skip_join(const double* rx, const double* ry, const int* leg_len, const long long* off, int npairs,
                                int max_pts, double* packed, hipStream_t stream);
 hipError_t af_launch_local_ops(const af::LocalOpsParams* P, hipStream_t stream);
+// cr_math.h's functions on n arguments, one per thread (fn 0 atan, 1 sin, 2 cos, 3 tan -> out;
+// 4 sincos -> out, out2): with the tables in global memory (utils.hip) and in LDS (cr_eval.hip)
+hipError_t af_launch_cr_eval(int fn, long long n, const double* x, double* out, double* out2, hipStream_t stream);
+hipError_t af_launch_cr_eval_lds(int fn, long long n, const double* x, double* out, double* out2, hipStream_t stream);
 hipError_t af_launch_mat_slowness(const af::DevModel* M, double* out, hipStream_t stream);
 hipError_t af_launch_tbp(const af::DevModel* M, int n, const double* x1, const double* x2, const double* y1,
                          const double* y2, double dnx, int sg, double* out, hipStream_t stream);

@@ -2,9 +2,11 @@
 // Anis_TTF_rays.py and device-level parity tests):
 //   update() / fouds18_A() on independent caller-supplied neighbourhoods (:904-1410, :240-901)
 //   time_between_points() on the resident model (:2835-2989)
+//   cr_math.h's atan / sin / cos / tan / sincos on caller-supplied arguments (global tables)
 #include "kernels.h"
 #include "local_ops.h"
 #include "band_common.h"
+#include "cr_eval.h"
 
 namespace af {
 
@@ -95,6 +97,26 @@ extern "C" hipError_t af_launch_tbp(const af::DevModel* M, int n, const double* 
 extern "C" hipError_t af_launch_mat_slowness(const af::DevModel* M, double* out, hipStream_t stream) {
   if (M->nmat <= 0) return hipSuccess;
   hipLaunchKernelGGL(af::mat_slowness_kernel, dim3((2 * M->nmat + 63) / 64), dim3(64), 0, stream, *M, out);
+  return hipGetLastError();
+}
+
+namespace af {
+// cr_math.h's functions as the operators call them (AF_ATAN ...), one argument per thread, with the
+// tables as this unit reads them: the global constants (cr_eval.hip: the same from LDS)
+__global__ void __launch_bounds__(kCrEvalThreads) cr_eval_kernel(int fn, long long n, const double* x, double* out,
+                                                                 double* out2) {
+  const long long k = (long long)blockIdx.x * kCrEvalThreads + threadIdx.x;
+  if (k >= n) return;
+  cr_eval_one(fn, x[k], out + k, out2 ? out2 + k : nullptr);
+}
+}  // namespace af
+
+extern "C" hipError_t af_launch_cr_eval(int fn, long long n, const double* x, double* out, double* out2,
+                                        hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  const unsigned blocks = af::cr_eval_blocks(n);
+  if (!blocks) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(af::cr_eval_kernel, dim3(blocks), dim3(af::kCrEvalThreads), 0, stream, fn, n, x, out, out2);
   return hipGetLastError();
 }
 

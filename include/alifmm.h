@@ -756,6 +756,15 @@ int alifmm_local_ops(alifmm_ctx* ctx, int op, int n, int pz, int px, const doubl
                      const int64_t* cell_velpn, const double* cell_vm, const int64_t* cell_stif,
                      const double* tab, int ncol, double* out);
 
+/* Evaluate the correctly rounded trigonometric functions every operator calls (csrc/cr_math.h) on
+ * n arguments, one per device thread: a device-level parity test like alifmm_local_ops.  fn 0 atan,
+ * 1 sin, 2 cos, 3 tan: out[i] = f(x[i]); fn 4 sincos: out[i] = sin, out2[i] = cos (out2 is required
+ * for fn 4 and ignored otherwise).  lds_tables 0: the kernel reads the functions' tables from global
+ * constants; 1: from LDS after crm::lds_init(), as the solver and ray kernels do.  n = 0 succeeds and
+ * launches nothing.  ALIFMM_E_ARG, with out / out2 untouched: fn or lds_tables out of range, n < 0,
+ * a null x / out (/ out2 for fn 4) with n > 0. */
+int alifmm_cr_math(alifmm_ctx* ctx, int fn, int lds_tables, int64_t n, const double* x, double* out, double* out2);
+
 /* fouds18_A() (:240-901) exactly as the band kernel evaluates it: the material of resident-model
  * cell (mz, mx) through the model's per-material record and its precomputed stencil slownesses
  * (quant 1: the subgrid > 1 view, orientation truncated to int32 and vel_map to float32, as
