@@ -68,6 +68,35 @@ AF_DEV void gst_sc1(T* p, T v) {
   __hip_atomic_store((AF_GLOBAL T*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Hand-shake words between two wavefront roles of one workgroup (the exact walks' heap role and
+// relax role): release stores, acquire polls.  A waiting role backs off between polls (s_sleep) so
+// that it takes no issue slots and LDS cycles from the working one, and gives up after 1 << 28
+// polls: a broken protocol ends as an error, not as a hang.
+AF_DEV void role_post(int* w, int v) { __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
+AF_DEV int role_load(int* w) { return __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
+AF_DEV bool role_await_value(int* w, int v) {  // false: timeout (the other role is gone)
+  for (long spins = 0; role_load(w) != v; spins++) {
+    __builtin_amdgcn_s_sleep(1);
+    if (spins > (1L << 28)) return false;
+  }
+  return true;
+}
+AF_DEV bool role_await_at_least(int* w, int v) {  // false: timeout
+  for (long spins = 0; role_load(w) < v; spins++) {
+    __builtin_amdgcn_s_sleep(1);
+    if (spins > (1L << 28)) return false;
+  }
+  return true;
+}
+AF_DEV int role_await_change(int* w, int last) {  // the next value != last, or -2 on timeout
+  for (long spins = 0;; spins++) {
+    const int v = role_load(w);
+    if (v != last) return v;
+    __builtin_amdgcn_s_sleep(1);
+    if (spins > (1L << 28)) return -2;
+  }
+}
+
 // value of lane l (wave-uniform l) for every lane: v_readlane into a scalar register, no LDS round
 // trip (a __shfl from one lane is a ds_bpermute: an LDS round trip in the wave's dependent chain)
 AF_DEV int bcast(int v, int l) { return __builtin_amdgcn_readlane(v, l); }

@@ -1,9 +1,9 @@
 // fmm_exact.hip — the source stages of travel_finer_grid() (Anis_TTF_rays.py:2187-2504) and the
 // first part of its fine-grid main loop (:2775-2817), solved exactly as the reference does, on gfx950.
 //
-// Near the source the reference's heap (round-half-even parent, SURVEY B-D3) pops nodes out of
-// time order, and the hand-over nodes and grid edges make the field depend on that order; a
-// time-ordered (band) solver differs there by up to a few per cent.  This kernel replays the
+// Near the source the reference's heap (walk_heap.h) pops nodes out of time order, and the
+// hand-over nodes and grid edges make the field depend on that order; a time-ordered (band)
+// solver differs there by up to a few per cent.  This kernel replays the
 // reference's heap walk: x9 stage grid, x3 stage grid, then the fine main grid until the heap
 // root reaches P.tstop.  The stage grids (up to 397 x 397 for subgrid 9) and the main grid live
 // in HBM; the heap itself (cells + keys, i.e. copies of ttn at insertion/update) lives in LDS, so
@@ -17,6 +17,8 @@
 #include "kernels.h"
 #include "local_ops.h"
 #include "fields.h"
+#include "walk_heap.h"
+#include "walk_rules.h"
 
 namespace af {
 
@@ -37,111 +39,21 @@ struct XLds {
   int cell[kXHeap];
   XSpec spec[kXSpec];
   int logc[kXLog];
-  int dup[8];  // XHeap's nodes with two heap entries (here, not in XHeap: see InitLds::dup)
+  int dup[8];  // the heap's nodes with two heap entries (here, not in XHeap: see InitLds::dup)
 };
+static_assert(sizeof(XLds) == 105504, "the LDS layout is fixed");
 
-// addtree / updtree / downtree (:94-237) over a global nsts array, heap slots in LDS.  Keys are
-// copies of ttn; a node with two heap entries (the stage-1 window corners, added by two of the
-// edge loops :2277-2288) has every entry's key refreshed when its ttn changes (dup / sync), as
-// the reference's comparisons read the live ttn.
+// The heap (walk_heap.h) with its slots in LDS: entries are flat cells, a node's heap index is its
+// status word in the grid's nsts array in HBM.
 constexpr int kXDup = 8;
-struct XHeap {
-  XLds* H;
-  int* S;
+struct XHeap : WalkHeap<WalkStatusStore<XLds, int, int, WalkFlatMap>, kXHeap, kXDup, 3> {
   const double* T;
-  int ntr;
-  int err;
-  int ndup = 0;
-  AF_DEV void setS(int c, int v) { S[c] = v; }
-  AF_DEV static int parent(int t) { return (int)rint((double)t / 2.0); }  // half-even (:123)
-  AF_DEV void swap(int a, int b) {
-    int c = H->cell[a];
-    H->cell[a] = H->cell[b];
-    H->cell[b] = c;
-    double k = H->key[a];
-    H->key[a] = H->key[b];
-    H->key[b] = k;
+  AF_DEV XHeap(XLds* H, int* S, const double* T_) : T(T_) {
+    s.m = H;
+    s.S = S;
   }
-  AF_DEV void sift_up(int c, int tpc) {
-    int tpp = parent(tpc);
-    const double tv = H->key[tpc];
-    while (tpp > 0) {
-      if (tv < H->key[tpp]) {
-        setS(c, tpp);
-        setS(H->cell[tpp], tpc);
-        swap(tpc, tpp);
-        tpc = tpp;
-        tpp = parent(tpc);
-      } else {
-        tpp = 0;
-      }
-    }
-  }
-  // key = the node's ttn; the relaxation passes the value it has just stored (no reload of T[c]);
-  // fresh: the node is known to be far (a relaxation of a far neighbour)
-  AF_DEV void add(int c, double key, bool fresh = false) {
-    ntr += 1;
-    if (ntr >= kXHeap) {
-      err = 3;
-      ntr = kXHeap - 1;
-      return;
-    }
-    if (!fresh && S[c] > 0) {  // already in the heap: a second entry
-      if (ndup == kXDup) {
-        err = 3;
-        return;
-      }
-      H->dup[ndup++] = c;
-    }
-    setS(c, ntr);
-    H->cell[ntr] = c;
-    H->key[ntr] = key;
-    sift_up(c, ntr);
-  }
-  AF_DEV void add(int c) { add(c, T[c]); }
-  // tpc: the node's heap index (its status, read by the caller before the relaxation)
-  AF_DEV void upd(int c, int tpc, double key) {
-    H->key[tpc] = key;
-    sift_up(c, tpc);
-  }
-  // node c's ttn is now key: every heap entry of a node with two entries takes it
-  AF_DEV void sync(int c, double key) {
-    bool d = false;
-    for (int k = 0; k < ndup; k++) d |= H->dup[k] == c;
-    if (!d) return;
-    for (int k = 1; k <= ntr; k++)
-      if (H->cell[k] == c) H->key[k] = key;
-  }
-  AF_DEV void down() {
-    if (ntr == 1) {
-      ntr -= 1;
-      return;
-    }
-    setS(H->cell[ntr], 1);
-    H->cell[1] = H->cell[ntr];
-    H->key[1] = H->key[ntr];
-    ntr -= 1;
-    int tpp = 1, tpc = 2;
-    while (tpc < ntr) {
-      if (H->key[tpc] > H->key[tpc + 1]) tpc = tpc + 1;
-      if (H->key[tpc] < H->key[tpp]) {
-        setS(H->cell[tpp], tpc);
-        setS(H->cell[tpc], tpp);
-        swap(tpc, tpp);
-        tpp = tpc;
-        tpc = 2 * tpp;
-      } else {
-        tpc = ntr + 1;
-      }
-    }
-    if (tpc == ntr) {
-      if (H->key[tpc] < H->key[tpp]) {
-        setS(H->cell[tpp], tpc);
-        setS(H->cell[tpc], tpp);
-        swap(tpc, tpp);
-      }
-    }
-  }
+  using WalkHeap::add;
+  AF_DEV void add(int c) { add(c, T[c], false); }
 };
 
 struct XGrid {
@@ -178,15 +90,15 @@ AF_DEV long long xloop_spec(XHeap& h, const DevModel& M, const XGrid& g, bool st
   long long pops = 0;
   bool finished = false;
   const int nz = g.nz, nx = g.nx;
-  XLds* X = h.H;
+  XLds* X = h.s.m;
   int mver = 0;  // relaxations logged (wave-uniform)
   long long npass = 0;
   X->spec[lane].cell = -1;
   while (true) {
     int go = 0, c = 0;
     if (lane == 0) {
-      go = h.ntr > 0 && !finished && !h.err && !(tstop > 0 && h.H->key[1] >= tstop);
-      c = h.H->cell[1];
+      go = h.ntr > 0 && !finished && !h.err && !(tstop > 0 && X->key[1] >= tstop);
+      c = X->cell[1];
     }
     go = __shfl(go, 0);
     if (!go) break;
@@ -196,11 +108,10 @@ AF_DEV long long xloop_spec(XHeap& h, const DevModel& M, const XGrid& g, bool st
     // the add / upd of earlier neighbours only move heap indices (positive stays positive) and touch
     // no other neighbour's far / known state, so the reference's per-neighbour classification
     // (far -1 -> add, close > 0 -> upd, known 0 -> skip) can be read up front
-    const int kz = lane == 2 ? iz - 1 : lane == 3 ? iz + 1 : iz;
-    const int kx = lane == 0 ? ix - 1 : lane == 1 ? ix + 1 : ix;
-    const bool inb = lane < 4 && (lane < 2 ? (0 <= kx && kx <= nx - 1) : (0 <= kz && kz <= nz - 1));
-    const int st = inb ? g.S[kz * nx + kx] : 0;
-    const bool edge = lane < 4 && !inb && stage && (lane < 2 ? abs(isx_s - kx) : abs(isz_s - kz)) == max_dist + 1;
+    const WalkNode nb4 = walk_nbr(lane & 3, iz, ix);
+    const bool inb = lane < 4 && walk_in_grid(lane & 3, nb4, nz, nx);
+    const int st = inb ? g.S[nb4.z * nx + nb4.x] : 0;
+    const bool edge = lane < 4 && !inb && stage && walk_stage_stop(lane & 3, nb4, isz_s, isx_s, max_dist);
     const unsigned long long jm = __ballot(inb && st != 0);
     if (__ballot(edge) != 0ull) finished = true;
     int stk[4];
@@ -208,13 +119,13 @@ AF_DEV long long xloop_spec(XHeap& h, const DevModel& M, const XGrid& g, bool st
     for (int k = 0; k < 4; k++) stk[k] = __shfl(st, k);
     if (lane == 0) {
       g.S[c] = 0;
-      h.down();
+      h.pop_down();
       pops++;
     }
     for (int k = 0; k < 4; k++) {
       if (!((jm >> k) & 1ull)) continue;
-      const int rz = k == 2 ? iz - 1 : k == 3 ? iz + 1 : iz, rx = k == 0 ? ix - 1 : k == 1 ? ix + 1 : ix;
-      const int r = rz * nx + rx;
+      const WalkNode rn = walk_nbr(k, iz, ix);
+      const int rz = rn.z, rx = rn.x, r = rz * nx + rx;
       // a usable entry?
       const unsigned long long hm = __ballot(X->spec[lane].cell == r);
       bool use = false;
@@ -227,9 +138,7 @@ AF_DEV long long xloop_spec(XHeap& h, const DevModel& M, const XGrid& g, bool st
         for (int q = ev + lane; !clash && q < mver; q += 64) {
           const int m = X->logc[q & (kXLog - 1)];
           const int mz = m / nx, mx = m - mz * nx;
-          const int dz = abs(mz - rz), dx = abs(mx - rx);
-          clash = (dz + dx >= 1) && ((dz + dx <= 1) || (dz == 2 && dx == 0) || (dx == 2 && dz == 0) ||
-                                     (dz == 1 && dx == 1));
+          clash = stencil_holds(mz - rz, mx - rx);
         }
         use = __ballot(clash) == 0ull;
         v = ev_val;
@@ -248,11 +157,12 @@ AF_DEV long long xloop_spec(XHeap& h, const DevModel& M, const XGrid& g, bool st
         int cz = rz, cx = rx;
         bool cand = true;
         if (lane > 0) {
-          const int p = 1 + ((lane - 1) >> 2), d = (lane - 1) & 3;
-          const int hc = X->cell[p];
+          const WalkGuess gs = walk_guess(lane);
+          const int hc = X->cell[gs.entry];
           const int hz = hc / nx, hx = hc - hz * nx;
-          cz = hz + (d == 2 ? -1 : d == 3 ? 1 : 0);
-          cx = hx + (d == 0 ? -1 : d == 1 ? 1 : 0);
+          const WalkNode q = walk_nbr(gs.dir, hz, hx);
+          cz = q.z;
+          cx = q.x;
           cand = hc >= 0 && hc < nz * nx && cz >= 0 && cz < nz && cx >= 0 && cx < nx;
         }
         NbField nb;
@@ -283,8 +193,7 @@ AF_DEV long long xloop_spec(XHeap& h, const DevModel& M, const XGrid& g, bool st
         if (box) box->add(rz, rx);
         g.T[r] = v;
         if (stk[k] == -1) h.add(r, v, true);
-        else h.upd(r, g.S[r], v);  // its heap index now (earlier sift-ups may have moved it)
-        if (h.ndup) h.sync(r, v);
+        else h.upd(g.S[r], r, v);  // its heap index now (earlier sift-ups may have moved it)
         X->logc[mver & (kXLog - 1)] = r;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the commit before any later load
       }
@@ -308,17 +217,9 @@ AF_DEV void xhandover(XHeap& h, const XGrid& s, int isz_s, int isx_s, const XGri
       const int dc = pz * d.nx + px;
       d.T[dc] = s.T[i * s.nx + j];
       if (box) box->add(pz, px);
-      const int st = s.S[i * s.nx + j];
-      if (st == 0) {
-        d.S[dc] = 0;
-        bool outer = false;
-        if (i - 3 >= 0) { if (s.S[(i - 3) * s.nx + j] == -1) outer = true; } else outer = true;
-        if (i + 3 <= s.nz - 1) { if (s.S[(i + 3) * s.nx + j] == -1) outer = true; } else outer = true;
-        if (j - 3 >= 0) { if (s.S[i * s.nx + j - 3] == -1) outer = true; } else outer = true;
-        if (j + 3 <= s.nx - 1) { if (s.S[i * s.nx + j + 3] == -1) outer = true; } else outer = true;
-        if (outer) h.add(dc);
-      }
-      if (st > 0) h.add(dc);
+      const int cls = handover_class([&](int z, int x) { return s.S[z * s.nx + x]; }, i, j, s.nz, s.nx);
+      if (cls == 1 || cls == 2) d.S[dc] = 0;
+      if (cls >= 2) h.add(dc);
     }
   }
 }
@@ -365,7 +266,7 @@ __global__ __launch_bounds__(64) void fmm_exact_kernel(BandParams P) {
     const int isx_s = scale * (int)(isx - left), isz_s = scale * (int)(isz - bottom);
     xclear(g.T, g.S, g.nz * g.nx);
     __syncthreads();
-    XHeap h{&lds, g.S, g.T, 0, 0};
+    XHeap h(&lds, g.S, g.T);
     if (stg == 0) {
       // straight rays (:2223-2267; veln + angle, SURVEY B-D5), material of the source's fine cell
       const int side1 = (9 - 1) / 2 + 9 * ((sg - 1) / 2);
@@ -424,7 +325,7 @@ __global__ __launch_bounds__(64) void fmm_exact_kernel(BandParams P) {
     g.mv = MatView{sg, sgside, 0, sg, sgside, 0, 1, 0, 0, 0, 1};
     g.dnx = P.dnx;  // the coarse spacing on the fine grid (:2790; field divided by sg at the end)
     g.dnz = P.dnz;
-    XHeap h{&lds, g.S, g.T, 0, 0};
+    XHeap h(&lds, g.S, g.T);
     XBox box;  // what the K-member band kernel copies into its edge buffers
     if (!err && lane == 0) {
       xhandover(h, prev, pisz, pisx, g, (int)isz, (int)isx, &box);

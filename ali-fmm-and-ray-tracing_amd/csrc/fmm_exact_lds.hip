@@ -20,14 +20,16 @@
 //     it changed) without any memory access.  Only relaxations with no entry cost a memory round
 //     trip: one evaluation pass in which lane 0 evaluates the job and the other lanes guesses (the
 //     neighbours of the heap's first 16 entries), as in fmm_exact.hip.
-// The walk, its heap (round-half-even parent, SURVEY B-D3), duplicate entries (the stage-1 window
-// corners, :2277-2288) and the hand-over order are fmm_exact.hip's, which reproduces the
-// reference's; results are bit-identical to it (tests/test_gpu_parity.py weld sg 3 / 9 fields,
+// The walk, its heap (walk_heap.h, shared), duplicate entries (the stage-1 window corners,
+// :2277-2288) and the hand-over order are fmm_exact.hip's, which reproduces the reference's;
+// results are bit-identical to it (tests/test_gpu_parity.py weld sg 3 / 9 fields,
 // tools/weld_split.py --dump).  Larger grids (subgrid > 9) and heap overflows use fmm_exact.hip.
 #define CR_LDS_TABLES  // cr_math.h tables in LDS (crm::lds_init at kernel start)
 #include "kernels.h"
 #include "local_ops.h"
 #include "fields.h"
+#include "walk_heap.h"
+#include "walk_rules.h"
 
 namespace af {
 namespace xl {
@@ -43,10 +45,7 @@ constexpr int kHT = 1 << kHTLog;  // hash slots (node -> heap index)
 constexpr int kDec = 18432;       // decimated nodes of a stage grid (hand-over classes)
 constexpr int kDup = 8;           // nodes with two heap entries
 
-constexpr unsigned kLive = 1u << 30, kTomb = 0x80000000u;  // hash words: live | pos << 18 | node
-constexpr unsigned kNodeM = (1u << 18) - 1;
-constexpr unsigned kDupF = 0x80000000u;  // heap entry: node | hash slot << 18 | kDupF
-constexpr unsigned kSFar = 0, kSClose = 1, kSKnown = 2;
+constexpr unsigned kSFar = kWalkFar, kSClose = kWalkClose, kSKnown = kWalkKnown;  // 2-bit status codes
 
 struct Lds {
   unsigned st[kCap / 16];
@@ -64,13 +63,7 @@ struct Lds {
   int job[4];
   double jval[4];
 };
-
-AF_DEV double rlane(double v, int l) {
-  const long long b = __double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)b, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), l);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
+static_assert(sizeof(Lds) == 147568, "the LDS layout is fixed: the walk has no room to spare");
 
 AF_DEV unsigned sget(const Lds* L, int c) { return (L->st[c >> 4] >> ((c & 15) * 2)) & 3u; }
 AF_DEV void sset(Lds* L, int c, unsigned v) {  // any previous state (LDS atomics: lanes share words)
@@ -78,8 +71,6 @@ AF_DEV void sset(Lds* L, int c, unsigned v) {  // any previous state (LDS atomic
   atomicAnd(&L->st[c >> 4], ~(3u << sh));
   if (v) atomicOr(&L->st[c >> 4], v << sh);
 }
-
-AF_DEV unsigned hslot(int c) { return ((unsigned)c * 2654435761u) >> (32 - kHTLog); }
 
 // the grid of a walk: T in HBM (row-major nz x nx, far = NaN), statuses of the window rows
 // [wz0, wz0 + wh), columns [wx0, wx0 + ww) in LDS (stage grids: the whole grid)
@@ -110,163 +101,38 @@ struct XField {
   }
 };
 
-// addtree / updtree / downtree (:94-237) with the heap indices (nsts > 0) in the LDS hash.  A heap
-// index write (setpos) is one LDS store through the entry's hash slot; an entry of a node with two
-// heap entries (kDupF) also makes the node close again, as the reference's nsts = index does after
-// the node was popped through its other entry.  Lane 0 only.
-struct Heap {
+// The heap (walk_heap.h) with its heap indices (nsts > 0) in the LDS hash (WalkHashStore).  Lane 0
+// only.  The store's device side: the status codes' accesses, and both reads of a heap slot kept
+// in one LDS round trip (not the entry after the key's compare).
+struct HeapDev {
   Lds* L;
-  int ntr = 0, err = 0, ndup = 0;
-  int livedup = 0;  // heap entries carrying kDupF
-  AF_DEV static int parent(int t) {  // round(t / 2), half-even (:123)
-    const int m = t >> 1;
-    return (t & 1) ? ((m & 1) ? m + 1 : m) : m;
+  AF_DEV unsigned get(int c) const { return sget(L, c); }
+  AF_DEV void set(int c, unsigned v) const { sset(L, c, v); }
+  AF_DEV void pin(unsigned& e) const { asm volatile("" : "+v"(e)); }
+  AF_DEV void pin(unsigned& e1, unsigned& e2) const { asm volatile("" : "+v"(e1), "+v"(e2)); }
+};
+using HeapStore = WalkHashStore<Lds, HeapDev, kHTLog>;
+// the store's words, which rehash() and the kernel's outputs read: hash words live | pos << 18 |
+// node, heap entries node | hash slot << 18 | kDupF
+constexpr unsigned kLive = HeapStore::kLive, kTomb = HeapStore::kTomb, kNodeM = HeapStore::kNodeM,
+                   kDupF = HeapStore::kDupF;
+static_assert(kHeap <= 1 << 12 && kCap <= 1 << 18 && kHTLog <= 13, "the words' fields hold them");
+struct Heap : WalkHeap<HeapStore, kHeap, kDup, 9> {
+  AF_DEV explicit Heap(Lds* L) {
+    s.m = L;
+    s.dev.L = L;
   }
-  AF_DEV bool isdup(int c) const {
-    bool d = false;
-    for (int k = 0; k < ndup; k++) d |= L->dup[k] == c;
-    return d;
-  }
-  AF_DEV int hfind(int c) const {
-    unsigned s = hslot(c);
-    for (int p = 0; p < kHT; p++) {
-      const unsigned w = L->ht[s];
-      if (w == 0u) return -1;
-      if ((w >> 30) == 1u && (int)(w & kNodeM) == c) return (int)s;
-      s = (s + 1) & (kHT - 1);
-    }
-    return -1;
-  }
-  AF_DEV int hinsert(int c) {
-    unsigned s = hslot(c);
-    while (true) {
-      const unsigned w = L->ht[s];
-      if (w == 0u || w == kTomb) {
-        if (w == 0u) L->nused++;
-        L->ht[s] = kLive | (unsigned)c;
-        return (int)s;
-      }
-      s = (s + 1) & (kHT - 1);
-    }
-  }
-  AF_DEV int pos_of(int c) const { return (int)((L->ht[hfind(c)] >> 18) & 0xfffu); }
-  AF_DEV void setpos(unsigned e, int pos) {
-    L->ht[(e >> 18) & (kHT - 1)] = kLive | ((unsigned)pos << 18) | (e & kNodeM);
-    if (e & kDupF) sset(L, (int)(e & kNodeM), kSClose);
-  }
-  AF_DEV void sift_up(int tpc, double km) {
-    const unsigned em = L->ent[tpc];
-    int tpp = parent(tpc);
-    while (tpp > 0) {
-      const double kp = L->key[tpp];
-      unsigned ep = L->ent[tpp];
-      asm volatile("" : "+v"(ep));  // both reads in one LDS round trip (not the entry after the compare)
-      if (!(km < kp)) break;
-      setpos(em, tpp);
-      setpos(ep, tpc);
-      L->ent[tpc] = ep;
-      L->key[tpc] = kp;
-      tpc = tpp;
-      tpp = parent(tpc);
-    }
-    L->ent[tpc] = em;
-    L->key[tpc] = km;
-  }
-  // key = the node's ttn; fresh: the node is far (a relaxation of a far neighbour)
-  AF_DEV void add(int c, double key, bool fresh) {
-    ntr += 1;
-    if (ntr >= kHeap) {
-      err = 9;
-      ntr = kHeap - 1;
-      return;
-    }
-    const unsigned s0 = fresh ? kSFar : sget(L, c);
-    unsigned e;
-    if (s0 == kSClose) {  // already in the heap: a second entry
-      if (ndup == kDup) {
-        err = 9;
-        return;
-      }
-      L->dup[ndup++] = c;
-      const int hs = hfind(c);
-      for (int k = 1; k < ntr; k++)  // its other entries now carry the flag
-        if ((int)(L->ent[k] & kNodeM) == c && !(L->ent[k] & kDupF)) {
-          L->ent[k] |= kDupF;
-          livedup++;
-        }
-      e = (unsigned)c | ((unsigned)hs << 18) | kDupF;
-    } else {
-      int hs = fresh ? -1 : hfind(c);  // a popped node with two entries keeps its slot
-      if (hs < 0) hs = hinsert(c);
-      e = (unsigned)c | ((unsigned)hs << 18) | (!fresh && isdup(c) ? kDupF : 0u);
-      sset(L, c, kSClose);
-    }
-    if (e & kDupF) livedup++;
-    L->ent[ntr] = e;
-    setpos(e, ntr);
-    sift_up(ntr, key);
-  }
-  // returns whether the node has another heap entry (its keys then follow, sync)
-  AF_DEV bool upd(int c, double key) {
-    const int tpc = pos_of(c);
-    L->key[tpc] = key;
-    const bool d = (L->ent[tpc] & kDupF) != 0u;
-    sift_up(tpc, key);
-    return d;
-  }
-  // node c (with two heap entries) has ttn key now: every entry of it takes it
-  AF_DEV void sync(int c, double key) {
-    for (int k = 1; k <= ntr; k++)
-      if ((int)(L->ent[k] & kNodeM) == c) L->key[k] = key;
+  using WalkHeap::upd;
+  AF_DEV void upd(int c, double key) {
+    const int tpc = s.pos_of(c);
+    upd(tpc, s.m->ent[tpc], key);
   }
   // pop the root in two parts: its status -> known; then its heap-index slot freed (unless the
   // node has another entry) and downtree
-  AF_DEV void pop_known() { sset(L, (int)(L->ent[1] & kNodeM), kSKnown); }
+  AF_DEV void pop_known() { sset(s.m, (int)(s.m->ent[1] & kNodeM), kSKnown); }
   AF_DEV void pop_rest() {
-    const unsigned e0 = L->ent[1];
-    if (!(e0 & kDupF)) L->ht[(e0 >> 18) & (kHT - 1)] = kTomb;
-    else livedup--;
-    if (ntr == 1) {
-      ntr = 0;
-      return;
-    }
-    const unsigned em = L->ent[ntr];
-    const double km = L->key[ntr];
-    setpos(em, 1);
-    ntr -= 1;
-    int tpp = 1, tpc = 2;
-    while (tpc < ntr) {
-      const double k1 = L->key[tpc], k2 = L->key[tpc + 1];
-      unsigned e1 = L->ent[tpc], e2 = L->ent[tpc + 1];
-      asm volatile("" : "+v"(e1), "+v"(e2));  // keys and entries in one LDS round trip
-      const bool right = k1 > k2;
-      const int t = right ? tpc + 1 : tpc;
-      const double kc = right ? k2 : k1;
-      const unsigned ec = right ? e2 : e1;
-      if (kc < km) {
-        setpos(em, t);
-        setpos(ec, tpp);
-        L->ent[tpp] = ec;
-        L->key[tpp] = kc;
-        tpp = t;
-        tpc = 2 * tpp;
-      } else {
-        tpc = ntr + 1;
-      }
-    }
-    if (tpc == ntr) {
-      const double kc = L->key[tpc];
-      const unsigned ec = L->ent[tpc];
-      if (kc < km) {
-        setpos(em, tpc);
-        setpos(ec, tpp);
-        L->ent[tpp] = ec;
-        L->key[tpp] = kc;
-        tpp = tpc;
-      }
-    }
-    L->ent[tpp] = em;
-    L->key[tpp] = km;
+    s.leave(s.m->ent[1]);
+    pop_down();
   }
 };
 
@@ -279,7 +145,7 @@ AF_DEV void rehash(Lds* L, Heap& h, int lane) {
   int dpos = -1, dnode = -1;
   if (lane < nd) {
     dnode = L->dup[lane];
-    unsigned s = hslot(dnode);
+    unsigned s = HeapStore::hslot(dnode);
     for (int p = 0; p < kHT; p++) {
       const unsigned w = L->ht[s];
       if (w == 0u) break;
@@ -294,7 +160,7 @@ AF_DEV void rehash(Lds* L, Heap& h, int lane) {
   for (int k = 1 + lane; k <= ntr; k += 64) {
     const unsigned e = L->ent[k];
     const int c = (int)(e & kNodeM);
-    unsigned s = hslot(c);
+    unsigned s = HeapStore::hslot(c);
     while (true) {
       const unsigned prev = atomicCAS(&L->ht[s], 0u, kLive | ((unsigned)k << 18) | (unsigned)c);
       if (prev == 0u || (int)(prev & kNodeM) == c) break;
@@ -304,7 +170,7 @@ AF_DEV void rehash(Lds* L, Heap& h, int lane) {
   }
   // popped nodes with two entries keep a slot even with no entry left
   if (lane < nd && dpos >= 0) {
-    unsigned s = hslot(dnode);
+    unsigned s = HeapStore::hslot(dnode);
     while (true) {
       const unsigned prev = atomicCAS(&L->ht[s], 0u, kLive | ((unsigned)dpos << 18) | (unsigned)dnode);
       if (prev == 0u) break;
@@ -336,8 +202,7 @@ struct Spec {
 AF_DEV void patch(Lds* L, Spec& sp, int rz, int rx, double v, int lane) {
   if (sp.c < 0) return;
   const int dz = rz - sp.z, dx = rx - sp.x;
-  const int ad = abs(dz) + abs(dx);
-  if (ad == 0 || ad > 2 || (dz != 0 && dx != 0 && (abs(dz) != 1 || abs(dx) != 1))) return;
+  if (!stencil_holds(dz, dx)) return;
   const int k = NbField::slot(dz, dx);
   L->stn[k][lane] = v;
   sp.vm |= 1u << k;
@@ -386,17 +251,18 @@ AF_DEV double relax_value(Lds* L, const DevModel& M, const XG& g, Spec& sp, int 
         sp.dirty = false;
       }
     }
-    return rlane(sp.v, e);
+    return lane_d(sp.v, e);
   }
   npass++;
   int cz = rz, cx = rx;
   bool cand = true;
   if (lane > 0) {
-    const int p = 1 + ((lane - 1) >> 2), d = (lane - 1) & 3;
-    const int hc = (int)(L->ent[p] & kNodeM);
-    cz = g.gz(hc) + (d == 2 ? -1 : d == 3 ? 1 : 0);
-    cx = g.gx(hc) + (d == 0 ? -1 : d == 1 ? 1 : 0);
-    cand = p <= ntr && cz >= 0 && cz < g.nz && cx >= 0 && cx < g.nx && g.inw(cz, cx) &&
+    const WalkGuess gs = walk_guess(lane);
+    const int hc = (int)(L->ent[gs.entry] & kNodeM);
+    const WalkNode q = walk_nbr(gs.dir, g.gz(hc), g.gx(hc));
+    cz = q.z;
+    cx = q.x;
+    cand = gs.entry <= ntr && cz >= 0 && cz < g.nz && cx >= 0 && cx < g.nx && g.inw(cz, cx) &&
            sget(L, g.loc(cz, cx)) != kSKnown;
   }
   if (cand) {
@@ -416,7 +282,7 @@ AF_DEV double relax_value(Lds* L, const DevModel& M, const XG& g, Spec& sp, int 
   } else {
     sp.c = -1;
   }
-  return rlane(sp.v, 0);
+  return lane_d(sp.v, 0);
 }
 
 // ---- the heap walk (:2292-2346, :2460-2504, :2775-2817) over two wavefronts ----
@@ -434,24 +300,6 @@ AF_DEV double relax_value(Lds* L, const DevModel& M, const XG& g, Spec& sp, int 
 // while such entries are in the heap (Heap::livedup) the heap runs downtree before posting the
 // jobs and the relax side waits for the earlier jobs' addtree / updtree before a fouds18_A() —
 // the sequential order.
-AF_DEV void xpost(int* w, int v) { __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
-AF_DEV int xload(int* w) { return __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
-// polls back off with s_sleep
-AF_DEV bool xawait_at_least(int* w, int v) {  // false: timeout (the other role is gone)
-  for (long spins = 0; xload(w) < v; spins++) {
-    __builtin_amdgcn_s_sleep(1);
-    if (spins > (1L << 28)) return false;
-  }
-  return true;
-}
-AF_DEV int xawait_change(int* w, int last) {  // the next value != last, or -2 on timeout
-  for (long spins = 0;; spins++) {
-    const int v = xload(w);
-    if (v != last) return v;
-    __builtin_amdgcn_s_sleep(1);
-    if (spins > (1L << 28)) return -2;
-  }
-}
 
 // heap wavefront (every lane; lane 0 holds the heap).  Returns the pops.
 AF_DEV long long heap_role(Lds* L, Heap& h, const XG& g, bool stage, int isx_s, int isz_s, int max_dist,
@@ -483,11 +331,10 @@ AF_DEV long long heap_role(Lds* L, Heap& h, const XG& g, bool stage, int isx_s, 
       if (lane == 0) h.err = 9;
       break;
     }
-    const int kz = lane == 2 ? iz - 1 : lane == 3 ? iz + 1 : iz;
-    const int kx = lane == 0 ? ix - 1 : lane == 1 ? ix + 1 : ix;
-    const bool inb = lane < 4 && (lane < 2 ? (0 <= kx && kx <= g.nx - 1) : (0 <= kz && kz <= g.nz - 1));
-    const unsigned st = inb ? sget(L, g.loc(kz, kx)) : kSKnown;
-    const bool edge = lane < 4 && !inb && stage && (lane < 2 ? abs(isx_s - kx) : abs(isz_s - kz)) == max_dist + 1;
+    const WalkNode nb4 = walk_nbr(lane & 3, iz, ix);
+    const bool inb = lane < 4 && walk_in_grid(lane & 3, nb4, g.nz, g.nx);
+    const unsigned st = inb ? sget(L, g.loc(nb4.z, nb4.x)) : kSKnown;
+    const bool edge = lane < 4 && !inb && stage && walk_stage_stop(lane & 3, nb4, isz_s, isx_s, max_dist);
     const unsigned long long jm = __ballot(inb && st != kSKnown);
     if (__ballot(edge) != 0ull) finished = true;
     const unsigned long long fm = __ballot(inb && st == kSFar);
@@ -495,19 +342,19 @@ AF_DEV long long heap_role(Lds* L, Heap& h, const XG& g, bool stage, int isx_s, 
     pops++;
     if (lane == 0) {
       h.pop_known();  // the popped node is known before any relaxation of this pop (fouds18_A)
-      const bool serial = h.livedup > 0;
+      const bool serial = h.s.livedup > 0;
       if (serial || n == 0) h.pop_rest();
       if (n > 0) {
         int q = 0;
         for (int k = 0; k < 4; k++) {
           if (!((jm >> k) & 1ull)) continue;
-          const int rz = k == 2 ? iz - 1 : k == 3 ? iz + 1 : iz, rx = k == 0 ? ix - 1 : k == 1 ? ix + 1 : ix;
-          L->job[q++] = g.loc(rz, rx) | (((fm >> k) & 1ull) ? (int)0x80000000 : 0);
+          const WalkNode rn = walk_nbr(k, iz, ix);
+          L->job[q++] = g.loc(rn.z, rn.x) | (((fm >> k) & 1ull) ? (int)0x80000000 : 0);
         }
         L->njob = n;
         L->serial = serial ? 1 : 0;
         L->ntr_hint = h.ntr;
-        xpost(&L->cmd, ++seq);
+        role_post(&L->cmd, ++seq);
         long long t1 = AF_XL_DIAG ? clock64() : 0;
         if (AF_XL_DIAG) dg[3] += t1 - tl;
         if (!serial) h.pop_rest();  // downtree beside the relaxations
@@ -517,7 +364,7 @@ AF_DEV long long heap_role(Lds* L, Heap& h, const XG& g, bool stage, int isx_s, 
           t1 = t2;
         }
         for (int q2 = 0; q2 < n; q2++) {
-          if (!xawait_at_least(&L->done, jobs + q2 + 1)) {
+          if (!role_await_at_least(&L->done, jobs + q2 + 1)) {
             h.err = 10;
             break;
           }
@@ -527,8 +374,8 @@ AF_DEV long long heap_role(Lds* L, Heap& h, const XG& g, bool stage, int isx_s, 
           const int r = jw & 0x7fffffff;
           const double v = L->jval[q2];
           if (jw < 0) h.add(r, v, true);
-          else if (h.upd(r, v)) h.sync(r, v);
-          xpost(&L->applied, jobs + q2 + 1);
+          else h.upd(r, v);
+          role_post(&L->applied, jobs + q2 + 1);
           if (AF_XL_DIAG) {
             t1 = clock64();
             dg[2] += t1 - t3;
@@ -539,7 +386,7 @@ AF_DEV long long heap_role(Lds* L, Heap& h, const XG& g, bool stage, int isx_s, 
       }
     }
   }
-  if (lane == 0) xpost(&L->cmd, -1);
+  if (lane == 0) role_post(&L->cmd, -1);
   if (AF_XL_DIAG && lane == 0)
     for (int k = 0; k < 4; k++) dgo[k] += dg[k];
   return pops;
@@ -555,7 +402,7 @@ AF_DEV void relax_role(Lds* L, const DevModel& M, const XG& g, Spec& sp, int lan
   while (true) {
     int cmd = 0;
     const long long tw = AF_XL_DIAG ? clock64() : 0;
-    if (lane == 0) cmd = xawait_change(&L->cmd, last);
+    if (lane == 0) cmd = role_await_change(&L->cmd, last);
     cmd = __shfl(cmd, 0);
     const long long tw2 = AF_XL_DIAG ? clock64() : 0;
     if (AF_XL_DIAG) dg[0] += tw2 - tw;
@@ -571,15 +418,15 @@ AF_DEV void relax_role(Lds* L, const DevModel& M, const XG& g, Spec& sp, int lan
       nrel++;
       if (lane == 0) {
         if (v == -1.0) {
-          if (serial) xawait_at_least(&L->applied, jobs + q);  // the earlier jobs' heap updates first
+          if (serial) role_await_at_least(&L->applied, jobs + q);  // the earlier jobs' heap updates first
           const XField F{L, &g};
           v = fouds18(F, M, cell_mat(M, g.mv, rz, rx), rz, rx, g.dnx, g.dnz, g.nx, g.nz, mat_slo(M, g.mv, rz, rx));
         }
         gst(g.T + (long)rz * g.nx + rx, v);
         L->jval[q] = v;
-        xpost(&L->done, jobs + q + 1);
+        role_post(&L->done, jobs + q + 1);
       }
-      v = rlane(v, 0);
+      v = lane_d(v, 0);
       patch(L, sp, rz, rx, v, lane);
     }
     jobs += n;
@@ -601,19 +448,12 @@ AF_DEV void classify(Lds* L, int nz, int nx, int tid) {
   const int dz = (nz - 1) / 3 + 1, dx = (nx - 1) / 3 + 1;
   for (int k = tid; k < dz * dx; k += kThreads) {
     const int i = 3 * (k / dx), j = 3 * (k % dx);
-    const unsigned s = sget(L, i * nx + j);
-    signed char cls = 0;
-    if (s == kSKnown) {
-      bool outer = false;
-      if (i - 3 >= 0) { if (sget(L, (i - 3) * nx + j) == kSFar) outer = true; } else outer = true;
-      if (i + 3 <= nz - 1) { if (sget(L, (i + 3) * nx + j) == kSFar) outer = true; } else outer = true;
-      if (j - 3 >= 0) { if (sget(L, i * nx + j - 3) == kSFar) outer = true; } else outer = true;
-      if (j + 3 <= nx - 1) { if (sget(L, i * nx + j + 3) == kSFar) outer = true; } else outer = true;
-      cls = outer ? 2 : 1;
-    } else if (s == kSClose) {
-      cls = 3;
-    }
-    L->dec[k] = cls;
+    // the 2-bit codes as the reference's statuses: far -1, known 0, close > 0
+    const auto status_at = [&](int z, int x) {
+      const unsigned s = sget(L, z * nx + x);
+      return s == kSKnown ? 0 : s == kSClose ? 1 : -1;
+    };
+    L->dec[k] = (signed char)handover_class(status_at, i, j, nz, nx);
   }
 }
 
@@ -653,7 +493,7 @@ AF_DEV void handover(Lds* L, Heap& h, const double* sT, int snz, int snx, int is
       const int l = __ffsll((long long)am) - 1;
       am &= am - 1;
       const int cl = __shfl(c, l);
-      const double tl = rlane(t, l);
+      const double tl = lane_d(t, l);
       if (lane == 0) h.add(cl, tl, false);
     }
   }
@@ -668,7 +508,7 @@ AF_DEV void add_run(Lds* L, Heap& h, const XG& g, int z0, int x0, int dz, int dx
     if (k < n) t = gld(g.T + (long)(z0 + k * dz) * g.nx + (x0 + k * dx));
     const int m = min(64, n - k0);
     for (int l = 0; l < m; l++) {
-      const double tl = rlane(t, l);
+      const double tl = lane_d(t, l);
       const int z = z0 + (k0 + l) * dz, x = x0 + (k0 + l) * dx;
       if (lane == 0) h.add(g.loc(z, x), tl, false);
     }
@@ -729,7 +569,7 @@ __global__ __launch_bounds__(kThreads) void fmm_exact_lds_kernel(BandParams P) {
     __syncthreads();
     h.ntr = 0;
     h.ndup = 0;
-    h.livedup = 0;
+    h.s.livedup = 0;
     if (stg == 0) {
       // straight rays (:2223-2267; veln + angle, SURVEY B-D5), material of the source's fine cell
       const int side1 = (9 - 1) / 2 + 9 * ((sg - 1) / 2);
@@ -811,7 +651,7 @@ __global__ __launch_bounds__(kThreads) void fmm_exact_lds_kernel(BandParams P) {
     if (w0) {
       h.ntr = 0;
       h.ndup = 0;
-      h.livedup = 0;
+      h.s.livedup = 0;
       handover(L, h, pT, pnz, pnx, pisz, pisx, g, (int)isz, (int)isx, lane);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }

@@ -2,8 +2,8 @@
 //
 // One workgroup per source, two wavefronts.  The three refined stage grids (5x5 coarse window x27,
 // 13x13 x9, 27x27 x3; <= 109x109 nodes) live entirely in LDS (154 KB of the CU's 160 KB) and
-// are solved with the reference's own heap-ordered FMM: the heap (with its round-half-even parent,
-// SURVEY B-D3), the stage-1 nnz=nnx1 quirk (:1645, padded reads) and the hand-over order are
+// are solved with the reference's own heap-ordered FMM: the heap (walk_heap.h), the walk's small
+// rules (walk_rules.h), the stage-1 nnz=nnx1 quirk (:1645, padded reads) and the hand-over order are
 // reproduced exactly, so the init region is the reference's up to device transcendental ulps.
 // The heap walk is inherently serial: wavefront 0 runs the heap (its sifts on one lane, a pop's
 // neighbour classification on four), wavefront 1 relaxes each pop's neighbours while the heap
@@ -18,6 +18,8 @@
 #include "kernels.h"
 #include "fields.h"
 #include "init_sig.h"
+#include "walk_heap.h"
+#include "walk_rules.h"
 
 namespace af {
 
@@ -54,10 +56,10 @@ struct InitLds {
   double T[kInitMaxN];
   double decT[kInitDec];
   short S[kInitMaxN];
-  double hkey[kInitHeap];          // heap keys: ttn of the node (kept equal to it by add/upd)
+  double key[kInitHeap];            // heap keys: ttn of the node (kept equal to it by add/upd)
   MatRec mat[kInitMat];
   double stab[5 * kInitStab];       // DevModel::stab (nstab <= kInitStab)
-  unsigned short hcell[kInitHeap];  // heap nodes (z << 8) | x
+  unsigned short cell[kInitHeap];   // heap nodes (z << 8) | x
   unsigned short dup[8];            // Heap: nodes with two heap entries (in LDS, not in the Heap
                                     // object: a dynamically indexed member would put the whole heap
                                     // state, LDS pointer included, in scratch -> flat LDS accesses)
@@ -73,6 +75,9 @@ struct InitLds {
   long long dg[12];                 // diagnostic build: shader-clock cycles per activity (AF_DG)
 #endif
 };
+#if !AF_INIT_DIAG
+static_assert(sizeof(InitLds) == 152960, "the LDS layout is fixed: the stage grids fill the CU's LDS");
+#endif
 
 struct LdsField {
   const double* T;
@@ -82,124 +87,28 @@ struct LdsField {
   AF_DEV double tt(long z, long x) const { return z >= nz ? 0.0 : T[z * nx + x]; }
 };
 
-// addtree / updtree / downtree (:94-237).  Keys are stored in the heap next to the node (a copy
-// of its ttn, refreshed by every add/upd), so a sift level is one LDS read instead of two
-// dependent ones; comparisons are exactly the reference's.  The reference compares live ttn, so
-// a node with two heap entries (the stage-1 window corners, added by two of the edge loops
-// :1601-1612) has both entries' keys change when its ttn does: such nodes are recorded (dup) and
-// every key of theirs is refreshed with their ttn (sync).
+// The heap (walk_heap.h) over this kernel's LDS: entries are nodes z << 8 | x, a node's heap index
+// is its status word in InitLds::S.
 constexpr int kInitDup = 8;
-struct Heap {
+struct Heap : WalkHeap<WalkStatusStore<InitLds, unsigned short, short, WalkPackedMap>, kInitHeap, kInitDup, 1> {
   InitLds* L;
   int nz, nx;
-  int ntr;
-  int err;
-  int ndup = 0;
   int pops = 0;
-  AF_DEV int bz(int k) const { return L->hcell[k] >> 8; }
-  AF_DEV int bx(int k) const { return L->hcell[k] & 255; }
-  AF_DEV double tb(int k) const { return L->hkey[k]; }
-  // round(t / 2), half-even (:123), in integer arithmetic
-  AF_DEV static int parent(int t) {
-    const int m = t >> 1;
-    return (t & 1) ? m + (m & 1) : m;
+  AF_DEV Heap(InitLds* l, int nz_, int nx_) : L(l), nz(nz_), nx(nx_) {
+    s.m = l;
+    s.S = l->S;
+    s.map.nx = nx_;
   }
-  AF_DEV void sift(int iz, int ix, int tpc) { sift_up(iz, ix, tpc); }
-  // The moving entry stays in registers while it sifts: one round of LDS reads per level (the
-  // other entry's key and node), the status writes in the reference's order.
-  AF_DEV void sift_up(int iz, int ix, int tpc) {
-    const unsigned short mc = (unsigned short)((iz << 8) | ix);
-    const double tv = L->hkey[tpc];
-    int tpp = parent(tpc);
-    while (tpp > 0) {
-      const double kp = L->hkey[tpp];
-      const unsigned short cp = L->hcell[tpp];
-      if (!(tv < kp)) break;
-      L->S[iz * nx + ix] = (short)tpp;
-      L->S[(cp >> 8) * nx + (cp & 255)] = (short)tpc;
-      L->hcell[tpc] = cp;
-      L->hkey[tpc] = kp;
-      tpc = tpp;
-      tpp = parent(tpc);
-    }
-    L->hcell[tpc] = mc;
-    L->hkey[tpc] = tv;
-  }
-  // addtree :94-138
+  AF_DEV int bz(int k) const { return L->cell[k] >> 8; }
+  AF_DEV int bx(int k) const { return L->cell[k] & 255; }
+  AF_DEV double tb(int k) const { return L->key[k]; }
   // fresh: the node is known to be far (a relaxation job; its status already reads 1, set by
   // the relax role), else its status tells whether it already has an entry
   AF_DEV void add(int iz, int ix, bool fresh = false) { add_key(iz, ix, L->T[iz * nx + ix], fresh); }
   // the same with the node's ttn given (read when its relaxation was posted)
-  AF_DEV void add_key(int iz, int ix, double key, bool fresh) {
-    ntr += 1;
-    if (ntr >= kInitHeap) { err = 1; ntr = kInitHeap - 1; return; }
-    if (!fresh && L->S[iz * nx + ix] > 0) {  // already in the heap: a second entry
-      if (ndup == kInitDup) { err = 1; return; }
-      L->dup[ndup++] = (unsigned short)((iz << 8) | ix);
-    }
-    L->S[iz * nx + ix] = (short)ntr;
-    L->hcell[ntr] = (unsigned short)((iz << 8) | ix);
-    L->hkey[ntr] = key;
-    sift(iz, ix, ntr);
-  }
-  // updtree :141-175
-  AF_DEV void upd(int iz, int ix) { upd_key(iz, ix, L->T[iz * nx + ix]); }
+  AF_DEV void add_key(int iz, int ix, double key, bool fresh) { WalkHeap::add((iz << 8) | ix, key, fresh); }
   AF_DEV void upd_key(int iz, int ix, double key) {
-    const int tpc = L->S[iz * nx + ix];
-    L->hkey[tpc] = key;
-    sift(iz, ix, tpc);
-  }
-  // a node's ttn changed: every heap entry of a node with two entries takes the new value
-  AF_DEV void sync(int iz, int ix) {
-    const unsigned short c = (unsigned short)((iz << 8) | ix);
-    bool d = false;
-    for (int k = 0; k < ndup; k++) d |= L->dup[k] == c;
-    if (!d) return;
-    const double t = L->T[iz * nx + ix];
-    for (int k = 1; k <= ntr; k++)
-      if (L->hcell[k] == c) L->hkey[k] = t;
-  }
-  AF_DEV void pop_down() { down(); }
-  // downtree :178-237 (the moving entry in registers, as in sift_up)
-  AF_DEV void down() {
-    if (ntr == 1) { ntr -= 1; return; }
-    const unsigned short mc = L->hcell[ntr];
-    const double km = L->hkey[ntr];
-    const int ms = (mc >> 8) * nx + (mc & 255);
-    L->S[ms] = 1;
-    ntr -= 1;
-    int tpp = 1, tpc = 2;
-    while (tpc < ntr) {
-      const double k1 = L->hkey[tpc], k2 = L->hkey[tpc + 1];
-      const unsigned short c1 = L->hcell[tpc], c2 = L->hcell[tpc + 1];
-      const bool right = k1 > k2;
-      const int t = right ? tpc + 1 : tpc;
-      const double kc = right ? k2 : k1;
-      const unsigned short cc = right ? c2 : c1;
-      if (kc < km) {
-        L->S[ms] = (short)t;
-        L->S[(cc >> 8) * nx + (cc & 255)] = (short)tpp;
-        L->hcell[tpp] = cc;
-        L->hkey[tpp] = kc;
-        tpp = t;
-        tpc = 2 * tpp;
-      } else {
-        tpc = ntr + 1;
-      }
-    }
-    if (tpc == ntr) {
-      const double kc = L->hkey[tpc];
-      const unsigned short cc = L->hcell[tpc];
-      if (kc < km) {
-        L->S[ms] = (short)tpc;
-        L->S[(cc >> 8) * nx + (cc & 255)] = (short)tpp;
-        L->hcell[tpp] = cc;
-        L->hkey[tpp] = kc;
-        tpp = tpc;
-      }
-    }
-    L->hcell[tpp] = mc;
-    L->hkey[tpp] = km;
+    upd(L->S[iz * nx + ix], (unsigned short)((iz << 8) | ix), key);
   }
 };
 
@@ -284,31 +193,6 @@ AF_DEV int job_z(int j) { return (j >> 8) & 255; }
 AF_DEV int job_x(int j) { return j & 255; }
 AF_DEV int job_kind(int j) { return j >> 16; }
 AF_DEV int job_pack(int z, int x, int kind) { return (z << 8) | x | (kind << 16); }
-AF_DEV void post(int* w, int v) { __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
-// the waiting role backs off between polls (s_sleep) so that it does not take issue slots and
-// LDS cycles from the working one
-AF_DEV bool await_value(int* w, int v) {  // false: timeout (the other role is gone)
-  for (long spins = 0; __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != v; spins++) {
-    __builtin_amdgcn_s_sleep(1);
-    if (spins > (1L << 28)) return false;
-  }
-  return true;
-}
-AF_DEV bool await_at_least(int* w, int v) {  // false: timeout
-  for (long spins = 0; __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < v; spins++) {
-    __builtin_amdgcn_s_sleep(1);
-    if (spins > (1L << 28)) return false;
-  }
-  return true;
-}
-AF_DEV int await_change(int* w, int last) {  // the next value != last, or -2 on timeout
-  for (long spins = 0;; spins++) {
-    const int v = __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (v != last) return v;
-    __builtin_amdgcn_s_sleep(1);
-    if (spins > (1L << 28)) return -2;
-  }
-}
 
 // heap role, one pop: hand the classified neighbours to the relax role, downtree, then each
 // neighbour's addtree / updtree as soon as its relaxation is done (L->done counts relaxations), so
@@ -328,14 +212,14 @@ AF_DEV bool pop_two_role(Heap& h, int& seq, int& jobs, int n, bool posted, Early
   }
   if (!posted) {
     L->njob = n;
-    post(&L->cmd, ++seq);
+    role_post(&L->cmd, ++seq);
   }
   AF_DG_T0(td)
   h.pop_down();
   AF_DG_ADD(L, 1, td)
   for (int k = 0; k < n; k++) {
     AF_DG_T0(tw)
-    if (!await_at_least(&L->done, jobs + k + 1)) return false;
+    if (!role_await_at_least(&L->done, jobs + k + 1)) return false;
     AF_DG_ADD(L, 0, tw)
     AF_DG_T0(ta)
     const int jk = L->job[k];
@@ -344,7 +228,6 @@ AF_DEV bool pop_two_role(Heap& h, int& seq, int& jobs, int n, bool posted, Early
     if (k == n - 1) early(key, (jz << 8) | jx);
     if (job_kind(jk) & kJobAdd) h.add_key(jz, jx, key, true);
     else h.upd_key(jz, jx, key);
-    if (h.ndup) h.sync(jz, jx);
     AF_DG_ADD(L, 2, ta)
   }
   jobs += n;
@@ -362,9 +245,6 @@ struct RelaxWin {
   int quirk_nnz;          // update()'s nnz for quirk jobs (stage 1: nnx1, :1645)
   int has_quirk;          // this walk has quirk jobs (close x-neighbours in stage 1)
 };
-
-// v of lane l (l wave-uniform)
-AF_DEV double readlane_d(double v, int l) { return lane_d(v, l); }
 
 // lane k < 12: NbField slot k of (iz, ix) on an LDS grid (rows z0..z1, columns x0..x1, pitch w),
 // the value and validity NbFieldT::load_lds gives that slot; other lanes: (0, false)
@@ -410,7 +290,7 @@ AF_DEV void relax_role(InitLds* L, const DevModel& M, const MatView& mv, const M
   while (true) {
     int cmd = 0;
     AF_DG_T0(tcw)
-    if (lane == 0) cmd = await_change(&L->cmd, last);
+    if (lane == 0) cmd = role_await_change(&L->cmd, last);
     if (lane == 0) { AF_DG_ADD(L, 4, tcw) }
     cmd = __shfl(cmd, 0);
     if (cmd < 0) break;
@@ -461,16 +341,18 @@ AF_DEV void relax_role(InitLds* L, const DevModel& M, const MatView& mv, const M
         } else if (lane == 0) {
           AF_DG_CNT(L, 9)
         }
-        v = readlane_d(my_val, e);
+        v = lane_d(my_val, e);
         if (lane == 0) { AF_DG_ADD(L, 5, tv) }
       } else {  // one pass: this job on lane 0, guesses of the next pops' jobs on the others
         int cz = lz, cx = lx, cnnz = qnnz;
         bool cand = true;
         if (lane > 0) {
-          const int p = 1 + ((lane - 1) >> 2), d = (lane - 1) & 3;
-          const int hc = L->hcell[p];
-          cz = (hc >> 8) + (d == 2 ? -1 : d == 3 ? 1 : 0);
-          cx = (hc & 255) + (d == 0 ? -1 : d == 1 ? 1 : 0);
+          const WalkGuess gs = walk_guess(lane);
+          const int d = gs.dir;
+          const int hc = L->cell[gs.entry];
+          const WalkNode q = walk_nbr(d, hc >> 8, hc & 255);
+          cz = q.z;
+          cx = q.x;
           cand = cz >= 0 && cz <= wz && cx >= 0 && cx <= wx;
           const int st = cand ? (int)L->S[cz * R.w + cx] : 0;
           cand = cand && st != 0;
@@ -491,7 +373,7 @@ AF_DEV void relax_role(InitLds* L, const DevModel& M, const MatView& mv, const M
           my_cell = -1;
         }
         nburst++;
-        v = readlane_d(my_val, 0);
+        v = lane_d(my_val, 0);
         if (lane == 0) { AF_DG_ADD(L, 6, tv) }
       }
       if (lane == 0) {
@@ -504,12 +386,10 @@ AF_DEV void relax_role(InitLds* L, const DevModel& M, const MatView& mv, const M
         }
         L->T[lz * R.w + lx] = v;
         if (kind & kJobAdd) L->S[lz * R.w + lx] = 1;  // valid for the next relaxations (addtree sets the index)
-        post(&L->done, (int)(njobs + 1));
+        role_post(&L->done, (int)(njobs + 1));
       }
-      if (my_cell >= 0) {  // the committed node changes the stencils that hold it
-        const int dz = lz - (my_cell >> 8), dx = lx - (my_cell & 255), ad = abs(dz) + abs(dx);
-        if (ad >= 1 && ad <= 2 && !(dz != 0 && dx != 0 && (abs(dz) != 1 || abs(dx) != 1))) my_dirty = true;
-      }
+      // the committed node changes the stencils that hold it
+      if (my_cell >= 0 && stencil_holds(lz - (my_cell >> 8), lx - (my_cell & 255))) my_dirty = true;
       njobs++;
     }
     busy += wall_clock64() - t0;
@@ -535,11 +415,12 @@ AF_DEV void stage_loop(Heap& h, const DevModel& M, const StageCfg& c, int tid) {
       if (tid == 0) L->S[iz * nx + ix] = 0;
       // lane d < 4: neighbour d in the reference's order (x - 1, x + 1, z - 1, z + 1)
       const int d = tid & 3;
-      const int zz = d < 2 ? iz : (d == 2 ? iz - 1 : iz + 1), xx = d < 2 ? (d == 0 ? ix - 1 : ix + 1) : ix;
-      const bool inb = tid < 4 && (d < 2 ? (0 <= xx && xx <= nx - 1) : (0 <= zz && zz <= nz - 1));
+      const WalkNode q = walk_nbr(d, iz, ix);
+      const int zz = q.z, xx = q.x;
+      const bool inb = tid < 4 && walk_in_grid(d, q, nz, nx);
       const int st = inb ? (int)L->S[zz * nx + xx] : 0;
       const bool job = inb && (st == -1 || st > 0);
-      const bool out = tid < 4 && !inb && (d < 2 ? abs(c.isx - xx) : abs(c.isz - zz)) == c.max_dist + 1;
+      const bool out = tid < 4 && !inb && walk_stage_stop(d, q, c.isz, c.isx, c.max_dist);
       const unsigned long long jm = __ballot(job);
       fin = __ballot(out) != 0;
       if (job)
@@ -568,8 +449,8 @@ AF_DEV void stage_loop(Heap& h, const DevModel& M, const StageCfg& c, int tid) {
       // first.  The heap operations keep the reference's order (this sift-up, then the next pop's
       // downtree); the next pop's relaxations read ttn and validity only, which sift-ups never touch
       auto early = [&](double key, int cell) {
-        if (finished || h.err || h.ndup || h.ntr < 1 || key < L->hkey[1] ||
-            (int)L->hcell[1] == cell)
+        if (finished || h.err || h.ndup || h.ntr < 1 || key < L->key[1] ||
+            (int)L->cell[1] == cell)
           return;
         bool f2 = false;
         const int n2 = classify(f2);
@@ -577,12 +458,12 @@ AF_DEV void stage_loop(Heap& h, const DevModel& M, const StageCfg& c, int tid) {
         pre_fin = f2;
         if (n2 > 0) {
           L->njob = n2;
-          post(&L->cmd, ++seq);
+          role_post(&L->cmd, ++seq);
         }
       };
       if (!pop_two_role(h, seq, jobs, n, posted, early)) h.err = 1;
     }
-    post(&L->cmd, -1);
+    role_post(&L->cmd, -1);
   } else if (tid >= 64) {
     relax_role<LDSMAT>(L, M, c.mv, c.mw, RelaxWin{0, 0, nz - 1, nx - 1, nx, 0, 0, nz, nx, c.dnx, c.dnx, nx, c.quirk},
                        tid - 64);
@@ -595,21 +476,35 @@ AF_DEV void decimate(InitLds* L, int nz, int nx, int lane, int nl) {
   int dz = (nz - 1) / 3 + 1, dx = (nx - 1) / 3 + 1;
   for (int k = lane; k < dz * dx; k += nl) {
     int i = 3 * (k / dx), j = 3 * (k % dx);
-    int st = L->S[i * nx + j];
     L->decT[k] = L->T[i * nx + j];
-    signed char cls = 0;
-    if (st == 0) {
-      bool outer = false;
-      if (i - 3 >= 0) { if (L->S[(i - 3) * nx + j] == -1) outer = true; } else outer = true;
-      if (i + 3 <= nz - 1) { if (L->S[(i + 3) * nx + j] == -1) outer = true; } else outer = true;
-      if (j - 3 >= 0) { if (L->S[i * nx + j - 3] == -1) outer = true; } else outer = true;
-      if (j + 3 <= nx - 1) { if (L->S[i * nx + j + 3] == -1) outer = true; } else outer = true;
-      cls = outer ? 2 : 1;
-    } else if (st > 0) {
-      cls = 3;
-    }
-    L->decC[k] = cls;
+    L->decC[k] = (signed char)handover_class([&](int z, int x) { return (int)L->S[z * nx + x]; }, i, j, nz, nx);
   }
+}
+
+// Heap role's wavefront: the decimated previous grid (pnz x pnx, its source at (pisz, pisx)) into
+// the heap's grid, whose node (sz, sx) is the source, in row-major order (:1719-1753): ttn copied,
+// known nodes known, outer-known and close nodes into the heap.
+AF_DEV void hand_over(InitLds* L, Heap& h, int pnz, int pnx, int pisz, int pisx, int sz, int sx) {
+  const int dz = (pnz - 1) / 3 + 1, dx = (pnx - 1) / 3 + 1;
+  for (int k = 0; k < dz * dx; k++) {
+    const int i = 3 * (k / dx), j = 3 * (k % dx);
+    const int pz = sz + (i - pisz) / 3, px = sx + (j - pisx) / 3;
+    L->T[pz * h.nx + px] = L->decT[k];
+    const signed char cls = L->decC[k];
+    if (cls == 1 || cls == 2) L->S[pz * h.nx + px] = 0;
+    if (cls >= 2) h.add(pz, px);
+  }
+}
+
+// lane 0: the end of a source's output, n hand-over triples written
+AF_DEV void emit_finish(const InitLds* L, HandoverOut* O, int n, int err, bool sign, InitSig* G) {
+#if AF_INIT_DIAG
+  for (int k = 0; k < 8; k++) O->prof[8 + k] = L->dg[k];
+  for (int k = 0; k < 4; k++) O->prof[k] = L->dg[8 + k];  // (diagnostic builds: the stage ticks' slots)
+#endif
+  O->n = n;
+  O->err = err;
+  if (sign && !err) G->valid = 1;
 }
 
 AF_DEV void clear_grid(InitLds* L, int n, int lane, int nl) {
@@ -639,29 +534,18 @@ AF_DEV void main_prefix(Heap& h, const DevModel& M, const InitJob& J, int wz0, i
         break;
       L->S[lz * ww + lx] = 0;
       int n = 0;
-      for (int s = 0; s < 2; s++) {
-        const int i = s == 0 ? ix - 1 : ix + 1;
-        if (0 <= i && i <= nnx - 1) {
-          const int st = L->S[lz * ww + (i - wx0)];
-          if (st == -1 || st > 0) {
-            L->job[n] = job_pack(lz, i - wx0, st == -1 ? kJobAdd : kJobUpd);
-            n++;
-          }
-        }
-      }
-      for (int s = 0; s < 2; s++) {
-        const int i = s == 0 ? iz - 1 : iz + 1;
-        if (0 <= i && i <= nnz - 1) {
-          const int st = L->S[(i - wz0) * ww + lx];
-          if (st == -1 || st > 0) {
-            L->job[n] = job_pack(i - wz0, lx, st == -1 ? kJobAdd : kJobUpd);
-            n++;
-          }
+      for (int k = 0; k < 4; k++) {
+        const WalkNode q = walk_nbr(k, iz, ix);
+        if (!walk_in_grid(k, q, nnz, nnx)) continue;
+        const int st = L->S[(q.z - wz0) * ww + (q.x - wx0)];
+        if (st == -1 || st > 0) {
+          L->job[n] = job_pack(q.z - wz0, q.x - wx0, st == -1 ? kJobAdd : kJobUpd);
+          n++;
         }
       }
       if (!pop_two_role(h, seq, jobs, n)) h.err = 1;
     }
-    post(&L->cmd, -1);
+    role_post(&L->cmd, -1);
   } else if (tid >= 64) {
     relax_role<LDSMAT>(L, M, ident, pw, RelaxWin{wz0, wx0, wz1, wx1, ww, wz0, wx0, nnz, nnx, J.dnx, J.dnz, nnz, 0},
                        tid - 64);
@@ -804,7 +688,7 @@ __global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* job
     clear_grid(L, nz * nx, lane, nl);
     if (LDSMAT) load_smid(M, L, c.mw, lane, nl);
     __syncthreads();
-    Heap h{L, nz, nx, 0, 0};
+    Heap h(L, nz, nx);
     if (stg == 0) {
       // straight rays in the source cell footprint (:1546-1590), coarse material at the source
       const int side1 = (sg - 1) / 2;
@@ -838,16 +722,7 @@ __global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* job
           for (int i = max(0, isz_s - s1); i <= min(nz - 1, isz_s + s1); i++) h.add(i, isx_s + s1);
       }
     } else if (lane < 64) {
-      // hand-over from the decimated previous stage, in row-major order (:1719-1753)
-      int dz = (pnz - 1) / 3 + 1, dx = (pnx - 1) / 3 + 1;
-      for (int k = 0; k < dz * dx; k++) {
-        int i = 3 * (k / dx), j = 3 * (k % dx);
-        int pz = isz_s + (i - pisz) / 3, px = isx_s + (j - pisx) / 3;
-        L->T[pz * nx + px] = L->decT[k];
-        signed char cls = L->decC[k];
-        if (cls == 1 || cls == 2) L->S[pz * nx + px] = 0;
-        if (cls >= 2) h.add(pz, px);
-      }
+      hand_over(L, h, pnz, pnx, pisz, pisx, isz_s, isx_s);  // from the decimated previous stage
     }
     if (lane == 0) {  // control words of the two-role walk
       L->cmd = 0;
@@ -892,17 +767,9 @@ __global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* job
       const MidWin pw = wh * ww <= kInitWin ? MidWin{wz0, wx0, ww, wh} : MidWin{0, 0, 0, 0};
       if (LDSMAT && pw.w) load_smid(M, L, pw, lane, nl);
       __syncthreads();
-      Heap h{L, wh, ww, 0, 0};
+      Heap h(L, wh, ww);
       if (lane < 64) {
-        int dz = (pnz - 1) / 3 + 1, dx = (pnx - 1) / 3 + 1;
-        for (int k = 0; k < dz * dx; k++) {
-          int i = 3 * (k / dx), j = 3 * (k % dx);
-          int pz = (int)(isz + (i - pisz) / 3) - wz0, px = (int)(isx + (j - pisx) / 3) - wx0;
-          L->T[pz * ww + px] = L->decT[k];
-          signed char cls = L->decC[k];
-          if (cls == 1 || cls == 2) L->S[pz * ww + px] = 0;
-          if (cls >= 2) h.add(pz, px);
-        }
+        hand_over(L, h, pnz, pnx, pisz, pisx, (int)isz - wz0, (int)isx - wx0);
         L->cmd = 0;
         L->done = 0;
       }
@@ -931,13 +798,7 @@ __global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* job
           O->cls[n] = st == 0 ? 1 : 3;
           n++;
         }
-#if AF_INIT_DIAG
-        for (int k = 0; k < 8; k++) O->prof[8 + k] = L->dg[k];
-        for (int k = 0; k < 4; k++) O->prof[k] = L->dg[8 + k];  // (diagnostic builds: the stage ticks' slots)
-#endif
-        O->n = n;
-        O->err = err;
-        if (sign && !err) G->valid = 1;
+        emit_finish(L, O, n, err, sign, G);
       }
       return;
     }
@@ -956,13 +817,7 @@ __global__ __launch_bounds__(128) void fmm_init_kernel(DevModel M0, InitJob* job
       O->cls[n] = cls;
       n++;
     }
-#if AF_INIT_DIAG
-    for (int k = 0; k < 8; k++) O->prof[8 + k] = L->dg[k];
-    for (int k = 0; k < 4; k++) O->prof[k] = L->dg[8 + k];  // (diagnostic builds: the stage ticks' slots)
-#endif
-    O->n = n;
-    O->err = err;
-    if (sign && !err) G->valid = 1;
+    emit_finish(L, O, n, err, sign, G);
   }
 }
 
