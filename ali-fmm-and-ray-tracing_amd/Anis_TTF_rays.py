@@ -661,13 +661,54 @@ class ALI_FMM:
             txs, rxs = [res[i][1] for i in tx], [res[i][1] for i in rx]
         return txs, rxs
 
+    def analytic_fmc(self, fmc, fs=None, band=None):
+        """The analytic signal of real RF traces, made on the device (no counterpart in the
+        reference): scipy.signal.hilbert's definition over the smallest power of two >= nt points,
+        the traces zero-padded to it, optionally band-passed in the same pass
+        (_alifmm.Context.trace_spectral: one FFT filter per trace in float64 with a fixed operation
+        order, so the result is reproducible to the bit).  tfm(), tfm_coherence(), lsq_image() and
+        sparse_image() take complex analytic data; |tfm(analytic_fmc(rf), fs)| is the envelope image.
+
+        fmc: (..., nt) real, nt <= 8192.  band: None, or (f_lo, f_hi) or (f_lo, f_hi, taper) in
+        the unit of fs, 0 <= f_lo < f_hi <= fs / 2 (_alifmm.bandpass_response: flat inside, raised-
+        cosine edges of width taper outside, a quarter of the band's width by default); needs fs.
+        Returns complex64 for float32 data, else complex128, of fmc's shape.  Device 0."""
+        fmc = np.asarray(fmc)
+        if np.iscomplexobj(fmc):
+            raise ValueError("analytic_fmc: the data are complex already")
+        if fmc.ndim < 1 or fmc.shape[-1] < 1:
+            raise ValueError("analytic_fmc: fmc must have shape (..., nt)")
+        response = None
+        if band is not None:
+            if fs is None:
+                raise ValueError("analytic_fmc: band needs fs")
+            if len(band) not in (2, 3):
+                raise ValueError("analytic_fmc: band is (f_lo, f_hi) or (f_lo, f_hi, taper)")
+            nfft = 1 << (fmc.shape[-1] - 1).bit_length()
+            response = _alifmm.bandpass_response(nfft, fs, *band)
+        return self._ctx(0).trace_spectral(fmc, response=response, analytic=True)
+
+    def _front_end(self, what, fmc, fs, analytic, band):
+        """fmc as the imaging entry points pass it on: itself, or analytic_fmc() of it."""
+        if not analytic:
+            if band is not None:
+                raise ValueError("%s: band needs analytic=True" % what)
+            return fmc
+        if np.iscomplexobj(fmc):
+            raise ValueError("%s: analytic=True on complex data (they are analytic already)" % what)
+        return self.analytic_fmc(fmc, fs, band)
+
     def tfm(self, fmc, fs, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1, veln=None,
-            velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct", reflector=None):
+            velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct", reflector=None, analytic=False,
+            band=None):
         """Total-focusing-method image of full-matrix-capture data fmc[(a, b, t)] with the
         first-arrival travel-time fields as delay laws: I(p) = sum_ab w_ab s_ab(T_a(p) + T_b(p))
         (no counterpart in the reference, whose fields exist for this purpose).
 
         fmc: (len(tx), len(rx), nt) real RF or complex analytic data sampled at fs [Hz] from t0 [s].
+        analytic=True takes real RF and images analytic_fmc(fmc, fs, band) instead (made on the
+        device first; band as there), so the result is complex and its modulus the envelope image;
+        on complex data it is a ValueError.  With the defaults nothing is filtered.
         tx, rx: element indices into scx, scz (default: all).  weights: (len(tx), len(rx))
         apodisation or 0/1 pair mask.  window = (iz0, ix0, niz, nix) in pixels of `step` fine-grid
         nodes; None: the whole field.  Model arguments default to the object's stored arrays.
@@ -683,6 +724,7 @@ class ALI_FMM:
 
         One GPU (device 0) only: every GPU would need every field, and sharding the pixels over
         GPUs is not implemented."""
+        fmc = self._front_end("tfm", fmc, fs, analytic, band)
         txs, rxs = self._pair_slots("tfm", tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path, rx_path,
                                     reflector)
         return self._ctx(0).tfm(txs, rxs, fmc, fs, t0=t0, weights=weights, window=window, step=step,
@@ -690,7 +732,7 @@ class ALI_FMM:
 
     def tfm_coherence(self, fmc, fs, kind="pcf", power=1.0, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1,
                       subgrid_size=1, veln=None, velpn=None, vel_map=None, stif_den=None, tx_path="direct",
-                      rx_path="direct", reflector=None):
+                      rx_path="direct", reflector=None, analytic=False, band=None):
         """Coherence-weighted TFM image (no counterpart in the reference): tfm()'s image times
         factor ** power, the factor in [0, 1] measuring per pixel how well the aperture's
         contributions agree.  Grain noise adds up in the delay-and-sum almost as a flaw echo does,
@@ -701,13 +743,15 @@ class ALI_FMM:
         1 - sqrt(1 - |sum t / |t||² / n²) of Camacho, Parrilla and Fritsch (2009); n counts the
         pairs whose delay falls inside the trace.  power: the exponent p (0 gives tfm()'s image).
         fmc, fs, t0, tx, rx, weights, window, step, subgrid_size, the model arguments, tx_path,
-        rx_path and reflector: as in tfm(), with the same field computation and the same checks.
+        rx_path, reflector, analytic and band: as in tfm(), with the same field computation and the
+        same checks; analytic=True is how "pcf" takes real RF.
         Both sums are made in one pass over the fields on the device (_alifmm.Context.tfm_coh); the
         image and the factor come back and are multiplied here.
         Returns (image * factor ** power, factor): the image float64 (niz, nix) or complex128 for
         complex data, the factor float64 (niz, nix).
 
         One GPU (device 0) only, as tfm()."""
+        fmc = self._front_end("tfm_coherence", fmc, fs, analytic, band)
         txs, rxs = self._pair_slots("tfm_coherence", tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path,
                                     rx_path, reflector)
         image, factor = self._ctx(0).tfm_coh(txs, rxs, fmc, fs, kind=kind, t0=t0, weights=weights, window=window,
@@ -716,7 +760,7 @@ class ALI_FMM:
 
     def lsq_image(self, fmc, fs, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1, veln=None,
                   velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct", reflector=None, damp=0.0,
-                  smooth=0.0, max_iter=50, tol=1e-6, pulse=None, pulse_origin=0):
+                  smooth=0.0, max_iter=50, tol=1e-6, pulse=None, pulse_origin=0, analytic=False, band=None):
         """Least-squares image of full-matrix-capture data: the reflectivity map x on the pixel
         window that minimises |simulate_fmc(x) - fmc|² + damp² |x|² + smooth² |D x|², by CGLS from
         x = 0 (no counterpart in the reference).  A is simulate_fmc() without a pulse, Aᵀ is tfm()
@@ -729,7 +773,7 @@ class ALI_FMM:
 
         fmc, fs, t0, tx, rx, weights, window, step, subgrid_size, the model arguments, tx_path,
         rx_path and reflector: as in tfm(), with the same field computation and the same checks;
-        fmc is sent as float64 and every value must be finite.  The fields, the data and every
+        fmc is sent as float64 and every value must be finite; analytic and band as in tfm().  The fields, the data and every
         vector of the iteration stay on the device (_alifmm.Context.tfm_lsq); one image comes back.
         damp is absolute, not relative to the operator: |A|_2 is of the order sqrt(len(tx) len(rx)),
         and info["grad0"] = |Aᵀ fmc| gives the scale of the gradient the stop rule
@@ -739,6 +783,7 @@ class ALI_FMM:
         fixed order: two solves agree to rounding, not to the bit.
 
         One GPU (device 0) only, as tfm()."""
+        fmc = self._front_end("lsq_image", fmc, fs, analytic, band)
         txs, rxs = self._pair_slots("lsq_image", tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path, rx_path,
                                     reflector)
         return self._ctx(0).tfm_lsq(txs, rxs, fmc, fs, t0=t0, weights=weights, window=window, step=step,
@@ -748,7 +793,7 @@ class ALI_FMM:
     def sparse_image(self, fmc, fs, t0=0.0, tx=None, rx=None, weights=None, window=None, step=1, subgrid_size=1,
                      veln=None, velpn=None, vel_map=None, stif_den=None, tx_path="direct", rx_path="direct",
                      reflector=None, damp=0.0, smooth=0.0, max_iter=500, tol=1e-6, pulse=None, pulse_origin=0,
-                     lam_rel=0.1, lam=None, lipschitz=0.0, power_iters=20, restart=True):
+                     lam_rel=0.1, lam=None, lipschitz=0.0, power_iters=20, restart=True, analytic=False, band=None):
         """Sparsity-regularised image of full-matrix-capture data: the reflectivity map x on the
         pixel window that minimises ½ |simulate_fmc(x, pulse=pulse) - fmc|² + ½ damp² |x|² +
         ½ smooth² |D x|² + lam Σ_pixels |x_p| (no counterpart in the reference).  A weld's
@@ -757,7 +802,7 @@ class ALI_FMM:
         backtracking and gradient restart from x = 0, every vector on the device
         (_alifmm.Context.tfm_sparse); one image comes back.
 
-        The arguments of lsq_image(), and: lam_rel, the weight of the ℓ1 term in units of
+        The arguments of lsq_image() (analytic and band among them), and: lam_rel, the weight of the ℓ1 term in units of
         lam_max = max_p |(Aᵀ Pᵀ fmc)_p|, the smallest weight whose minimiser is 0 (the library takes
         it from its own first gradient); lam, the weight itself, which lam_rel gives way to;
         lipschitz, power_iters, restart: as in _alifmm.Context.tfm_sparse.
@@ -766,6 +811,7 @@ class ALI_FMM:
         backtracks, restarts, nnz).
 
         One GPU (device 0) only, as tfm()."""
+        fmc = self._front_end("sparse_image", fmc, fs, analytic, band)
         txs, rxs = self._pair_slots("sparse_image", tx, rx, subgrid_size, veln, velpn, vel_map, stif_den, tx_path, rx_path,
                                     reflector)
         return self._ctx(0).tfm_sparse(txs, rxs, fmc, fs, t0=t0, weights=weights, window=window, step=step,

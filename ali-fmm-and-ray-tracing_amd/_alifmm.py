@@ -95,6 +95,7 @@ def _load():
             "alifmm_tfm_sparse": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _i, _d, _d, _p, _i, _i, _i, _i, _i, _d, _d, _i, _d,
                                        _i, _i, _p, _i, _d, _d, _i, _i, _p, _p, _p]),
             "alifmm_trace_fir": (_i, [_p, _l, _i, _i, _p, _i, _i, _p, _i, _i, _p]),
+            "alifmm_trace_spectral": (_i, [_p, _l, _i, _i, _i, _p, _i, _i, _p, _i, _p]),
             "alifmm_ray_sens": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p]),
             "alifmm_sens_op_build": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
             "alifmm_sens_op_apply": (_i, [_p, _i, _p, _p]),
@@ -463,6 +464,40 @@ class Context:
         self._chk(lib().alifmm_trace_fir(self._h, x.size // nt if nt else 0, nt, nc, _ptr(x), taps.shape[0], taps.shape[1],
                                          _ptr(taps), int(origin), int(bool(transpose)), _ptr(out)), "trace_fir")
         return out.view(np.complex128)[..., 0] if cplx else out[..., 0]
+
+    def trace_spectral(self, data, response=None, analytic=False, nfft=None):
+        """Every trace of data filtered in the frequency domain on the device
+        (alifmm_trace_spectral): out = IDFT(G · DFT(data)) over nfft points, G the analytic mask
+        (analytic=True: scipy.signal.hilbert(data, N=nfft)[..., :nt]), the response, or both.  A
+        radix-2 transform in float64 with a written-out operation order (include/alifmm.h): the
+        result is reproducible to the bit and a trace does not depend on the others.
+
+        data: (..., nt) real or complex, nt <= 8192; float32 and complex64 are sent as float32, any
+        other dtype as float64.  nfft: a power of two in [nt, 8192]; None: the smallest one >= nt
+        (the trace is zero-padded to it and the result cut to nt).  response: None, or (nfft,) real
+        or complex, H_k at bin k in numpy.fft's order (bandpass_response() makes one), all finite.
+        Returns complex64 for float32 / complex64 data, else complex128, of data's shape."""
+        data = np.asarray(data)
+        if data.ndim < 1:
+            raise ValueError("trace_spectral: data must have shape (..., nt)")
+        cplx = np.iscomplexobj(data)
+        f32 = data.dtype in (np.float32, np.complex64)
+        x = np.ascontiguousarray(data, dtype=(np.complex64 if cplx else np.float32) if f32
+                                 else (np.complex128 if cplx else np.float64))
+        nt = x.shape[-1]
+        n = int(nfft) if nfft else 1 << max(nt - 1, 0).bit_length()
+        h, hc = None, 0
+        if response is not None:
+            response = np.asarray(response)
+            if response.shape != (n,):
+                raise ValueError("trace_spectral: response must have shape (nfft,) = (%d,), not %s" % (n, response.shape))
+            hc = 2 if np.iscomplexobj(response) else 1
+            h = np.ascontiguousarray(response, dtype=np.complex128 if hc == 2 else np.float64)
+        out = np.empty(x.shape, dtype=np.complex64 if f32 else np.complex128)
+        self._chk(lib().alifmm_trace_spectral(self._h, x.size // nt if nt else 0, nt, 2 if cplx else 1, int(f32), _ptr(x),
+                                              int(nfft) if nfft else 0, hc, _ptr(h), int(bool(analytic)), _ptr(out)),
+                  "trace_spectral")
+        return out
 
     def tfm_lsq(self, tx_slots, rx_slots, fmc, fs, t0=0.0, weights=None, window=None, step=1, subgrid=1, damp=0.0,
                 smooth=0.0, max_iter=50, tol=1e-6, resid=False, pulse=None, pulse_origin=0):
@@ -980,6 +1015,35 @@ class Comm:
 def gather_layout(counts):
     """Root slot offset of every rank's first field in alifmm_gather_fields (rank order)."""
     return np.concatenate(([0], np.cumsum(np.asarray(counts, dtype=np.int64))))[:-1]
+
+
+def bandpass_response(nfft, fs, f_lo, f_hi, taper=None):
+    """A real band-pass response for Context.trace_spectral: (nfft,) float64 in numpy.fft's bin
+    order, 1 for f_lo <= |f| <= f_hi, raised-cosine edges of width taper outside them
+    (0.5 (1 - cos(pi (|f| - f_lo + taper) / taper)) below f_lo, mirrored above f_hi), 0 beyond; the
+    same on positive and negative frequencies, so a real trace stays real.  Host numpy.
+
+    fs: the sampling rate; 0 <= f_lo < f_hi <= fs / 2; taper >= 0 in the same unit (None: a quarter
+    of the band's width; 0: a brick wall)."""
+    nfft, fs, f_lo, f_hi = int(nfft), float(fs), float(f_lo), float(f_hi)
+    if nfft < 1:
+        raise ValueError("bandpass_response: nfft %d" % nfft)
+    if not (fs > 0 and np.isfinite(fs)):
+        raise ValueError("bandpass_response: fs %g" % fs)
+    if not 0 <= f_lo < f_hi <= fs / 2:
+        raise ValueError("bandpass_response: band edges (%g, %g) are not 0 <= f_lo < f_hi <= fs / 2 = %g"
+                         % (f_lo, f_hi, fs / 2))
+    taper = (f_hi - f_lo) / 4 if taper is None else float(taper)
+    if not (taper >= 0 and np.isfinite(taper)):
+        raise ValueError("bandpass_response: taper %g" % taper)
+    f = np.abs(np.fft.fftfreq(nfft, 1.0 / fs))
+    h = ((f >= f_lo) & (f <= f_hi)).astype(np.float64)
+    if taper > 0:
+        lo = (f < f_lo) & (f > f_lo - taper)
+        hi = (f > f_hi) & (f < f_hi + taper)
+        h[lo] = 0.5 * (1 - np.cos(np.pi * (f[lo] - f_lo + taper) / taper))
+        h[hi] = 0.5 * (1 - np.cos(np.pi * (f_hi + taper - f[hi]) / taper))
+    return h
 
 
 _default = {}

@@ -281,6 +281,12 @@ struct alifmm_ctx {
     DevBuf<double> in, out, taps;
   } fir;
   double t_fir_upload = 0, t_fir_kernel = 0;  // last alifmm_trace_fir (ms)
+  // alifmm_trace_spectral: grow-only device buffers (the traces in and out, sized in doubles whatever
+  // the dtype; the response in element order), freed with the context
+  struct FftBufs {
+    DevBuf<double> in, out, resp;
+  } fft;
+  double t_fft_upload = 0, t_fft_kernel = 0, t_fft_download = 0;  // last alifmm_trace_spectral (ms)
   // alifmm_ray_sens: grow-only device buffers (a chunk of host points, the per-ray arrays of a
   // request, the three maps), freed with the context; the row arrays live for one call
   struct SensBufs {

@@ -81,6 +81,7 @@ extern "C" int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   ctx->tfm_lsq = {};
   ctx->tfm_sparse = {};
   ctx->fir = {};
+  ctx->fft = {};
   ctx->tfm_model = {};
   ctx->skip = {};
   ctx->sens = {};
@@ -210,6 +211,12 @@ extern "C" int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* valu
   else if (!strcmp(name, "trace_fir_upload_ms")) *value = ctx->t_fir_upload;
   else if (!strcmp(name, "trace_fir_kernel_ms")) *value = ctx->t_fir_kernel;
   else if (!strcmp(name, "trace_fir_tile")) *value = af_trace_fir_tile();
+  // last alifmm_trace_spectral call (ms): host -> device copies (host clock), the kernel (HIP events),
+  // the device -> host copy (host clock); the most workgroups a launch starts (a constant of the build)
+  else if (!strcmp(name, "trace_fft_upload_ms")) *value = ctx->t_fft_upload;
+  else if (!strcmp(name, "trace_fft_kernel_ms")) *value = ctx->t_fft_kernel;
+  else if (!strcmp(name, "trace_fft_download_ms")) *value = ctx->t_fft_download;
+  else if (!strcmp(name, "trace_fft_grid")) *value = af_trace_fft_grid();
   // last alifmm_travel_seeded call: the seed pass (uploads and fmm_seed_kernel, HIP events, ms), the
   // seeds and the close cells handed over per field
   else if (!strcmp(name, "seed_ms")) *value = ctx->t_seed;

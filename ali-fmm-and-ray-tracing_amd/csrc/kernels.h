@@ -9,6 +9,7 @@
 #include "tfm_solve_ops.h"  // af::TfmLsqDims: the vectors' shapes of the least-squares imaging solve (tfm_solve.hip)
 #include "tfm_sparse_ops.h"  // the scalars and partial arrays of sparsity-regularised imaging (tfm_sparse.hip)
 #include "trace_fir_term.h"  // the trace FIR's sum and tile walk (trace_fir.hip)
+#include "trace_fft_term.h"  // the spectral trace filter's arithmetic and passes (trace_fft.hip)
 
 namespace af {
 
@@ -231,6 +232,17 @@ struct TraceFirParams {
   int nt, ntap, origin, transpose;
 };
 
+// the spectral trace filter (trace_fft.hip): ntrace traces in [ntrace][S.nt][ncomp] -> out [ntrace][S.nt][2],
+// distinct device arrays of float64 or float32; hrev the response on the device in element order,
+// hrev[idx][S.resp_comp] = H[bitrev(idx)] (null: none)
+struct TraceFftParams {
+  const void* in;
+  void* out;
+  const double* hrev;
+  int64_t ntrace;
+  FftShape S;
+};
+
 }  // namespace af
 
 extern "C" {
@@ -322,4 +334,8 @@ hipError_t af_launch_tfm_sparse_final(const af::TfmLsqDims* G, const af::SparseV
 // 2 (2: ncomp 2), 1 <= ntap <= af::kFirMaxTaps, 0 <= origin < ntap.  af_trace_fir_tile: outputs per workgroup
 hipError_t af_launch_trace_fir(const af::TraceFirParams* P, int ncomp, int tap_comp, hipStream_t stream);
 int af_trace_fir_tile();
+// the spectral trace filter (trace_fft.hip; the arithmetic: trace_fft_term.h); ncomp 1 or 2, dtype 0 float64 or
+// 1 float32 (of in and out).  af_trace_fft_grid: the most workgroups a launch starts
+hipError_t af_launch_trace_fft(const af::TraceFftParams* P, int ncomp, int dtype, hipStream_t stream);
+int af_trace_fft_grid();
 }

@@ -511,6 +511,63 @@ int alifmm_tfm_lsq(alifmm_ctx* ctx, int subgrid, int ntx, const int32_t* tx_slot
 int alifmm_trace_fir(alifmm_ctx* ctx, int64_t ntrace, int nt, int ncomp, const double* in, int ntap, int tap_comp,
                      const double* taps, int origin, int transpose, double* out);
 
+/* The spectral trace filter: y = IDFT(G · DFT(x)) per trace on the device, G the analytic mask, the
+ * caller's frequency response, or both, in a fixed order of operations.  It makes real RF analytic
+ * (scipy.signal.hilbert's definition) and band-passes it in the same pass, which the imaging entry
+ * points expect of their complex data.
+ *   in                 [ntrace][nt][ncomp], ncomp 1 (real) or 2 (re, im interleaved)
+ *   dtype              0 float64, 1 float32: of in and of out
+ *   nfft               the transform length N: a power of two, nt <= N <= ALIFMM_FFT_MAX; 0: the
+ *                      smallest power of two >= nt
+ *   resp_comp, resp    0 and NULL: no response; else float64 [N][resp_comp], real (1) or complex (2):
+ *                      H_k at DFT bin k in numpy's bin order; every value finite
+ *   analytic           1: the mask m_0 = 1, m_{N/2} = 1 (N >= 2), m_k = 2 for 0 < k < N/2, 0 above
+ *                      (scipy.signal.hilbert(x, N=nfft)); 0: none
+ *   out                complex, [ntrace][nt][2], of the same dtype; may not be in
+ * Per trace, all in float64, operations in the order written, no contraction:
+ *   load      v[n] = x[n] for n < nt (a float32 sample converts exactly; a real sample gets
+ *             im = +0.0), (+0.0, +0.0) for nt <= n < N
+ *   twiddles  W_N^m = (c_m, -s_m), c_m = cos(2 pi m / N), s_m = sin(2 pi m / N) of the exact real
+ *             argument, each rounded once to nearest: the committed table csrc/fft_twiddles.h holds
+ *             sin(2 pi m / 8192), m = 0 .. 2048; the other quadrants and the cosines follow by exact
+ *             symmetry, and a smaller N reads the table with the stride 8192 / N (the same real
+ *             number, so the same bits)
+ *   product   a · w = ((ar * wr) - (ai * wi), (ar * wi) + (ai * wr)): each product rounded, then
+ *             the subtraction and the addition
+ *   forward   radix-2 decimation in frequency, in place: for l = 0 .. log2 N - 1, half = N >> (l+1),
+ *             every block of 2 half elements and i < half: a = v[p], b = v[p + half], v[p] = a + b,
+ *             d = a - b, v[p + half] = d · W_N^(i << l).  X_k now lies at v[bitrev(k)].
+ *   pointwise at v[bitrev(k)]: a complex H_k multiplies by the product above (w = H_k), a real one
+ *             scales both components; then the mask: (vr * 2, vi * 2) for 0 < k < N/2, (+0.0, +0.0)
+ *             for k > N/2, and nothing for m_k = 1 (the product with 1 changes no bit)
+ *   inverse   radix-2 decimation in time, from the bit-reversed order back to natural order: for
+ *             l = log2 N - 1 .. 0, the same pairs: a = v[p], b = v[p + half] · conj(W_N^(i << l)),
+ *             v[p] = a + b, v[p + half] = a - b
+ *   store     y[n] = (vr * (1 / N), vi * (1 / N)) for n < nt: the scaling is exact; rounded once to
+ *             float32 for dtype 1
+ * Every butterfly multiplies by its twiddle, W^0 = (1, -0) included: no product is skipped, in the
+ * kernel, in the numpy restatement (tests/trace_fft_ref.py) and in the host replay
+ * (tests/trace_fft_sim.cpp).  There is no permutation pass: the forward transform leaves the
+ * bit-reversed order and the inverse consumes it.  The kernel groups up to three layers into one
+ * pass over registers; an element still sees exactly these operations in this order.
+ * So a trace's result depends on nothing but that trace, N, resp and analytic, and is
+ * bit-reproducible between calls.  The data are not checked: a non-finite sample makes that trace's
+ * output unspecified and leaves the other traces alone.
+ * ALIFMM_E_ARG with a message, the context staying usable and out untouched: ctx, in or out NULL;
+ * out == in; ntrace < 1; nt < 1 or nt > ALIFMM_FFT_MAX; ncomp not 1 or 2; dtype not 0 or 1; nfft not
+ * 0 and not a power of two in [nt, ALIFMM_FFT_MAX]; resp_comp not 0, 1 or 2; resp NULL with
+ * resp_comp > 0 or given with resp_comp 0; a non-finite response value; analytic not 0 or 1; more
+ * traces than 64-bit byte offsets hold.
+ * Needs no model.  Upload, one kernel, download; the traces and the response live in grow-only
+ * device buffers of the context, freed with it.  All trace offsets are 64-bit.  alifmm_get_option:
+ * "trace_fft_upload_ms" (host -> device copies), "trace_fft_kernel_ms" (the kernel) and
+ * "trace_fft_download_ms" (the device -> host copy) of the last call; "trace_fft_grid", the most
+ * workgroups a launch starts (a constant of the build; a workgroup transforms
+ * max(1, min(512, 2048 / N)) traces at a time and walks the rest with the grid's stride).  One GPU. */
+#define ALIFMM_FFT_MAX 8192
+int alifmm_trace_spectral(alifmm_ctx* ctx, int64_t ntrace, int nt, int ncomp, int dtype, const void* in, int nfft,
+                          int resp_comp, const double* resp, int analytic, void* out);
+
 /* Pulse-aware least-squares imaging: alifmm_tfm_lsq with the pulse in the operator,
  * min |P A x - d|^2 + damp^2 |x|^2 + smooth^2 |D x|^2 by CGLS from x = 0.
  *   subgrid ... tol    as in alifmm_tfm_lsq
