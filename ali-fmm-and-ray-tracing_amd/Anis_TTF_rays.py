@@ -688,6 +688,67 @@ class ALI_FMM:
             response = _alifmm.bandpass_response(nfft, fs, *band)
         return self._ctx(0).trace_spectral(fmc, response=response, analytic=True)
 
+    def pick_times(self, fmc, fs, around, half_width, t0=0.0, mode="peak", frac=0.5, guard=None, analytic=True,
+                   band=None, pulse=None, pulse_origin=0):
+        """Measured times of flight from full-matrix-capture traces, picked on the device (no
+        counterpart in the reference): per pair (i, j) the envelope's peak (mode="peak") or its
+        first rise to frac of the peak (mode="onset") among the samples whose time lies within
+        half_width of the predicted time around[i, j], refined to a fraction of a sample
+        (_alifmm.Context.trace_pick; the rules are written out in include/alifmm.h, and the picks
+        are reproducible to the bit).  The traces are uploaded once, made analytic, band-passed
+        and matched-filtered in one pass on the device, and only the picks come back.  The
+        intended loop: times = find_all_TTF_rays(...); picked, info = pick_times(rf, fs,
+        around=times, half_width=...); tomography_step(picked - times, pairs=...).
+
+        fmc: (n, n, nt), sample k of a trace at time t0 + k / fs; real RF with analytic=True (the
+        default: scipy.signal.hilbert's definition, as analytic_fmc()), or complex analytic data
+        with analytic=False.  around: (n, n) predicted times [s], e.g. find_all_TTF_rays' return
+        value, _alifmm skip_pick times or a column of field values; NaN: the pair is not asked for.
+        The gate is _alifmm.pick_gates(around, half_width, t0, fs, nt).  band: None, (f_lo, f_hi) or
+        (f_lo, f_hi, taper) as in analytic_fmc().  pulse: None, or the transducer's pulse (1-D, its
+        time zero at tap pulse_origin, the convention of simulate_fmc()): the traces are correlated
+        with it (_alifmm.matched_response), so an echo peaks at its time zero.  With a pulse the
+        transform length is the smallest power of two >= nt + ntap - 1 if that is <= 8192, so the
+        correlation does not wrap; otherwise the smallest power of two >= nt, and up to ntap - 1
+        samples at either end of a trace see the other end.  guard: the runner-up lies more than
+        guard samples from the peak; None: the pulse's length, 0 without a pulse.
+        Returns (times, info): times (n, n) [s], NaN where the pair was not asked for or nothing
+        could be picked (flags 1 or 2); info: a dict of (n, n) arrays, "pos" (the pick in samples),
+        "amp", "ratio" (runner-up over peak amplitude, near 1 for an ambiguous pick; NaN without a
+        pick), "idx", "idx2" and "flags" (as trace_pick's).  Device 0."""
+        fmc = np.asarray(fmc)
+        if fmc.ndim != 3 or fmc.shape[0] != fmc.shape[1] or fmc.shape[-1] < 1:
+            raise ValueError("pick_times: fmc must have shape (n, n, nt)")
+        around = np.asarray(around, dtype=np.float64)
+        if around.shape != fmc.shape[:2]:
+            raise ValueError("pick_times: around must have shape (n, n) = %s" % (fmc.shape[:2],))
+        if analytic and np.iscomplexobj(fmc):
+            raise ValueError("pick_times: analytic=True on complex data (they are analytic already)")
+        nt = fmc.shape[-1]
+        nfft, response = 1 << (nt - 1).bit_length(), None
+        if pulse is not None:
+            pulse = np.asarray(pulse)
+            if pulse.ndim != 1 or len(pulse) < 1:
+                raise ValueError("pick_times: pulse must be a 1-D array")
+            full = 1 << (nt + len(pulse) - 2).bit_length()
+            if full <= 8192:
+                nfft = full
+            response = _alifmm.matched_response(nfft, pulse, pulse_origin)
+        if band is not None:
+            if len(band) not in (2, 3):
+                raise ValueError("pick_times: band is (f_lo, f_hi) or (f_lo, f_hi, taper)")
+            h = _alifmm.bandpass_response(nfft, fs, *band)
+            response = h if response is None else response * h
+        if guard is None:
+            guard = 0 if pulse is None else len(pulse)
+        lo, hi = _alifmm.pick_gates(around, half_width, t0, fs, nt)
+        filt = response is not None or bool(analytic)
+        pos, amp, idx, amp2, idx2, flags = self._ctx(0).trace_pick(
+            fmc, lo, hi, mode=mode, frac=frac, guard=guard, response=response, analytic=analytic, nfft=nfft if filt else None)
+        with np.errstate(all="ignore"):
+            ratio = np.where(amp > 0, amp2 / amp, np.nan)
+        return t0 + pos / fs, {"pos": pos, "amp": amp, "ratio": ratio, "idx": idx, "idx2": idx2, "flags": flags}
+
     def _front_end(self, what, fmc, fs, analytic, band):
         """fmc as the imaging entry points pass it on: itself, or analytic_fmc() of it."""
         if not analytic:

@@ -96,6 +96,8 @@ def _load():
                                        _i, _i, _p, _i, _d, _d, _i, _i, _p, _p, _p]),
             "alifmm_trace_fir": (_i, [_p, _l, _i, _i, _p, _i, _i, _p, _i, _i, _p]),
             "alifmm_trace_spectral": (_i, [_p, _l, _i, _i, _i, _p, _i, _i, _p, _i, _p]),
+            "alifmm_trace_pick": (_i, [_p, _l, _i, _i, _i, _p, _i, _i, _i, _p, _i, _p, _p, _i, _d, _i, _p, _p, _p, _p, _p,
+                                       _p]),
             "alifmm_ray_sens": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p, _p]),
             "alifmm_sens_op_build": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
             "alifmm_sens_op_apply": (_i, [_p, _i, _p, _p]),
@@ -477,27 +479,80 @@ class Context:
         (the trace is zero-padded to it and the result cut to nt).  response: None, or (nfft,) real
         or complex, H_k at bin k in numpy.fft's order (bandpass_response() makes one), all finite.
         Returns complex64 for float32 / complex64 data, else complex128, of data's shape."""
-        data = np.asarray(data)
-        if data.ndim < 1:
-            raise ValueError("trace_spectral: data must have shape (..., nt)")
-        cplx = np.iscomplexobj(data)
-        f32 = data.dtype in (np.float32, np.complex64)
-        x = np.ascontiguousarray(data, dtype=(np.complex64 if cplx else np.float32) if f32
-                                 else (np.complex128 if cplx else np.float64))
+        x, cplx, f32 = self._trace_args("trace_spectral", data)
         nt = x.shape[-1]
-        n = int(nfft) if nfft else 1 << max(nt - 1, 0).bit_length()
-        h, hc = None, 0
-        if response is not None:
-            response = np.asarray(response)
-            if response.shape != (n,):
-                raise ValueError("trace_spectral: response must have shape (nfft,) = (%d,), not %s" % (n, response.shape))
-            hc = 2 if np.iscomplexobj(response) else 1
-            h = np.ascontiguousarray(response, dtype=np.complex128 if hc == 2 else np.float64)
+        h, hc = self._response_args("trace_spectral", response, nt, nfft)
         out = np.empty(x.shape, dtype=np.complex64 if f32 else np.complex128)
         self._chk(lib().alifmm_trace_spectral(self._h, x.size // nt if nt else 0, nt, 2 if cplx else 1, int(f32), _ptr(x),
                                               int(nfft) if nfft else 0, hc, _ptr(h), int(bool(analytic)), _ptr(out)),
                   "trace_spectral")
         return out
+
+    @staticmethod
+    def _trace_args(what, data):
+        """Traces as trace_spectral and trace_pick send them: (contiguous array, complex, float32)."""
+        data = np.asarray(data)
+        if data.ndim < 1:
+            raise ValueError("%s: data must have shape (..., nt)" % what)
+        cplx = np.iscomplexobj(data)
+        f32 = data.dtype in (np.float32, np.complex64)
+        x = np.ascontiguousarray(data, dtype=(np.complex64 if cplx else np.float32) if f32
+                                 else (np.complex128 if cplx else np.float64))
+        return x, cplx, f32
+
+    @staticmethod
+    def _response_args(what, response, nt, nfft):
+        """A frequency response as the same two send it: (float64 or complex128 array or None, its
+        components 0, 1 or 2)."""
+        if response is None:
+            return None, 0
+        n = int(nfft) if nfft else 1 << max(nt - 1, 0).bit_length()
+        response = np.asarray(response)
+        if response.shape != (n,):
+            raise ValueError("%s: response must have shape (nfft,) = (%d,), not %s" % (what, n, response.shape))
+        hc = 2 if np.iscomplexobj(response) else 1
+        return np.ascontiguousarray(response, dtype=np.complex128 if hc == 2 else np.float64), hc
+
+    def trace_pick(self, data, gate_lo, gate_hi, mode="peak", frac=0.5, guard=0, response=None, analytic=False, nfft=None):
+        """Time-of-flight picks on the device (alifmm_trace_pick): per trace the largest |sample|
+        inside the gate [gate_lo, gate_hi) (mode="peak"), or the first sample of the gate that
+        reaches frac of it (mode="onset", 0 < frac <= 1), refined to a fraction of a sample, and the
+        largest |sample| more than guard samples away from the peak.  With a response or
+        analytic=True the traces first pass trace_spectral()'s filter (its arguments and limits)
+        and are picked where it left them on the device: only the picks come back, and they are,
+        to the bit, those of trace_pick(trace_spectral(data, ...), ...).  The rules are written out
+        operation by operation in include/alifmm.h: the picks are reproducible to the bit and a
+        trace does not depend on the others.
+
+        data: (..., nt) real or complex; float32 and complex64 are sent as float32, any other dtype
+        as float64.  gate_lo, gate_hi: integers shaped like data's leading dimensions (or
+        broadcastable to them), 0 <= lo, hi <= nt; lo >= hi: the trace is not asked for.
+        Returns (pos, amp, idx, amp2, idx2, flags), each shaped like the leading dimensions: the
+        pick in samples (NaN: none), the peak's amplitude and sample, the runner-up's amplitude and
+        sample (-1: none), and flags (1 no gate, 2 nothing to pick, 4 unrefined, 8 at the gate's
+        edge, 16 a non-finite sample in the gate)."""
+        x, cplx, f32 = self._trace_args("trace_pick", data)
+        nt = x.shape[-1]
+        lead = x.shape[:-1]
+        m = {"peak": 0, "onset": 1}.get(mode)
+        if m is None:
+            raise ValueError("trace_pick: mode must be 'peak' or 'onset'")
+        try:
+            lo = np.ascontiguousarray(np.broadcast_to(np.asarray(gate_lo), lead), dtype=np.int32)
+            hi = np.ascontiguousarray(np.broadcast_to(np.asarray(gate_hi), lead), dtype=np.int32)
+        except ValueError:
+            raise ValueError("trace_pick: the gates must have data's leading shape %s" % (lead,)) from None
+        filt = response is not None or bool(analytic)
+        h, hc = self._response_args("trace_pick", response, nt, nfft) if filt else (None, 0)
+        if not filt and nfft:
+            raise ValueError("trace_pick: nfft needs a response or analytic=True")
+        pos, amp, amp2 = (np.empty(lead) for _ in range(3))
+        idx, idx2, flags = (np.empty(lead, dtype=np.int32) for _ in range(3))
+        self._chk(lib().alifmm_trace_pick(self._h, x.size // nt if nt else 0, nt, 2 if cplx else 1, int(f32), _ptr(x),
+                                          int(filt), int(nfft) if nfft else 0, hc, _ptr(h), int(bool(analytic)), _ptr(lo),
+                                          _ptr(hi), m, float(frac), int(guard), _ptr(pos), _ptr(amp), _ptr(idx), _ptr(amp2),
+                                          _ptr(idx2), _ptr(flags)), "trace_pick")
+        return pos, amp, idx, amp2, idx2, flags
 
     def tfm_lsq(self, tx_slots, rx_slots, fmc, fs, t0=0.0, weights=None, window=None, step=1, subgrid=1, damp=0.0,
                 smooth=0.0, max_iter=50, tol=1e-6, resid=False, pulse=None, pulse_origin=0):
@@ -1044,6 +1099,57 @@ def bandpass_response(nfft, fs, f_lo, f_hi, taper=None):
         h[lo] = 0.5 * (1 - np.cos(np.pi * (f[lo] - f_lo + taper) / taper))
         h[hi] = 0.5 * (1 - np.cos(np.pi * (f_hi + taper - f[hi]) / taper))
     return h
+
+
+def matched_response(nfft, pulse, origin=0):
+    """The matched filter of a pulse as a response for Context.trace_spectral and trace_pick:
+    (nfft,) complex128 in numpy.fft's bin order, the frequency response of correlation with the
+    pulse, out[t] = sum_j conj(pulse[j]) in[t + j - origin] (Context.trace_fir(..., transpose=True),
+    circular over nfft points), divided by sum |pulse|^2, so an echo that is the pulse itself, its
+    time zero on sample n, peaks on sample n with the echo's amplitude.  Multiply it with
+    bandpass_response() to do both in one pass.  Host numpy.
+
+    The filter is circular: the output equals trace_fir's wherever no tap reaches over an end of
+    the nfft points, everywhere when nfft >= nt + ntap - 1 (the padding holds what wraps).
+    pulse: 1-D real or complex, 1 <= ntap <= nfft, finite, not all zero; origin: the tap index of
+    its time zero, 0 <= origin < ntap."""
+    nfft, origin = int(nfft), int(origin)
+    h = np.asarray(pulse)
+    if h.ndim != 1 or not 1 <= h.shape[0] <= nfft:
+        raise ValueError("matched_response: pulse must be 1-D with 1 .. nfft = %d taps, not %s" % (nfft, h.shape))
+    if not 0 <= origin < h.shape[0]:
+        raise ValueError("matched_response: origin %d outside [0, %d)" % (origin, h.shape[0]))
+    h = h.astype(np.complex128)
+    norm = float(np.sum(h.real ** 2 + h.imag ** 2))
+    if not (np.isfinite(norm) and norm > 0):
+        raise ValueError("matched_response: the pulse must be finite and not all zero")
+    g = np.zeros(nfft, dtype=np.complex128)  # the impulse response: conj(pulse[j]) at delay origin - j
+    np.add.at(g, (origin - np.arange(h.shape[0])) % nfft, np.conj(h))
+    return np.fft.fft(g) / norm
+
+
+def pick_gates(around, half_width, t0, fs, nt):
+    """The gates of ALI_FMM.pick_times: per entry of `around` (predicted times, any shape) the
+    samples n of a trace of nt samples, sample n at time t0 + n / fs, with
+    ceil((around - half_width - t0) fs) <= n <= floor((around + half_width - t0) fs), clipped to
+    0 .. nt - 1.  Returns (lo, hi) int32 of around's shape, the gate being lo <= n < hi; lo = hi = 0
+    where around is NaN or infinite or no sample of the trace lies inside."""
+    around = np.asarray(around, dtype=np.float64)
+    half_width, t0, fs, nt = float(half_width), float(t0), float(fs), int(nt)
+    if not (half_width >= 0 and np.isfinite(half_width)):
+        raise ValueError("pick_gates: half_width %g" % half_width)
+    if not (fs > 0 and np.isfinite(fs)) or not np.isfinite(t0):
+        raise ValueError("pick_gates: fs %g, t0 %g" % (fs, t0))
+    if nt < 1:
+        raise ValueError("pick_gates: nt %d" % nt)
+    ok = np.isfinite(around)
+    a = np.where(ok, around, 0.0)
+    first = np.maximum(np.ceil((a - half_width - t0) * fs), 0.0)
+    last = np.minimum(np.floor((a + half_width - t0) * fs), nt - 1.0)
+    ok &= first <= last
+    lo = np.where(ok, first, 0.0).astype(np.int32)
+    hi = np.where(ok, last + 1.0, 0.0).astype(np.int32)
+    return lo, hi
 
 
 _default = {}

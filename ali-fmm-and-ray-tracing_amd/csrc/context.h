@@ -287,6 +287,13 @@ struct alifmm_ctx {
     DevBuf<double> in, out, resp;
   } fft;
   double t_fft_upload = 0, t_fft_kernel = 0, t_fft_download = 0;  // last alifmm_trace_spectral (ms)
+  // alifmm_trace_pick: grow-only device buffers (the gates lo then hi; pos, amp, amp2; idx, idx2,
+  // flags), freed with the context.  Its traces live in fft.in and, filtered, in fft.out
+  struct PickBufs {
+    DevBuf<int> gates, outi;
+    DevBuf<double> outd;
+  } pick;
+  double t_pick_upload = 0, t_pick_filter = 0, t_pick_kernel = 0, t_pick_download = 0;  // last alifmm_trace_pick (ms)
   // alifmm_ray_sens: grow-only device buffers (a chunk of host points, the per-ray arrays of a
   // request, the three maps), freed with the context; the row arrays live for one call
   struct SensBufs {

@@ -82,6 +82,7 @@ extern "C" int alifmm_ctx_destroy(alifmm_ctx* ctx) {
   ctx->tfm_sparse = {};
   ctx->fir = {};
   ctx->fft = {};
+  ctx->pick = {};
   ctx->tfm_model = {};
   ctx->skip = {};
   ctx->sens = {};
@@ -217,6 +218,11 @@ extern "C" int alifmm_get_option(alifmm_ctx* ctx, const char* name, double* valu
   else if (!strcmp(name, "trace_fft_kernel_ms")) *value = ctx->t_fft_kernel;
   else if (!strcmp(name, "trace_fft_download_ms")) *value = ctx->t_fft_download;
   else if (!strcmp(name, "trace_fft_grid")) *value = af_trace_fft_grid();
+  else if (!strcmp(name, "trace_pick_upload_ms")) *value = ctx->t_pick_upload;
+  else if (!strcmp(name, "trace_pick_filter_ms")) *value = ctx->t_pick_filter;
+  else if (!strcmp(name, "trace_pick_kernel_ms")) *value = ctx->t_pick_kernel;
+  else if (!strcmp(name, "trace_pick_download_ms")) *value = ctx->t_pick_download;
+  else if (!strcmp(name, "trace_pick_grid")) *value = af_trace_pick_grid();
   // last alifmm_travel_seeded call: the seed pass (uploads and fmm_seed_kernel, HIP events, ms), the
   // seeds and the close cells handed over per field
   else if (!strcmp(name, "seed_ms")) *value = ctx->t_seed;

@@ -53,6 +53,13 @@ struct FirTaps {
 // data of ncomp components
 int fir_check_taps(alifmm_ctx* ctx, const char* what, int ncomp, const FirTaps& F);
 
+// ---- host_fft.cpp ----
+// alifmm_trace_spectral up to its download (`what` names the caller in messages): its checks of
+// these arguments, the upload into ctx->fft.in, the kernel; the filtered traces [ntrace][nt][2] of
+// the input's dtype are left in ctx->fft.out.  *t_upload, *t_kernel: the two parts (ms)
+int fft_front(alifmm_ctx* ctx, const char* what, int64_t ntrace, int nt, int ncomp, int dtype, const void* in, int nfft,
+              int resp_comp, const double* resp, int analytic, double* t_upload, double* t_kernel);
+
 // ---- timed sections ----
 // `launch(stream)` between the context's first two events, waited for; its device time into *ms
 template <class F>

@@ -10,6 +10,7 @@
 #include "tfm_sparse_ops.h"  // the scalars and partial arrays of sparsity-regularised imaging (tfm_sparse.hip)
 #include "trace_fir_term.h"  // the trace FIR's sum and tile walk (trace_fir.hip)
 #include "trace_fft_term.h"  // the spectral trace filter's arithmetic and passes (trace_fft.hip)
+#include "trace_pick_term.h"  // the time-of-flight picker's rules (trace_pick.hip)
 
 namespace af {
 
@@ -243,6 +244,20 @@ struct TraceFftParams {
   FftShape S;
 };
 
+// the time-of-flight picker (trace_pick.hip): ntrace traces in [ntrace][nt][ncomp] of float64 or float32
+// and a gate [lo[t], hi[t]) per trace on the device -> six outputs per trace; mode 0 peak, 1 onset
+// (0 < frac <= 1), guard >= 0
+struct TracePickParams {
+  const void* in;
+  const int* lo;
+  const int* hi;
+  int64_t ntrace;
+  int nt, mode, guard;
+  double frac;
+  double *pos, *amp, *amp2;
+  int *idx, *idx2, *flags;
+};
+
 }  // namespace af
 
 extern "C" {
@@ -338,4 +353,8 @@ int af_trace_fir_tile();
 // 1 float32 (of in and out).  af_trace_fft_grid: the most workgroups a launch starts
 hipError_t af_launch_trace_fft(const af::TraceFftParams* P, int ncomp, int dtype, hipStream_t stream);
 int af_trace_fft_grid();
+// the time-of-flight picker (trace_pick.hip; the rules: trace_pick_term.h); ncomp 1 or 2, dtype 0 float64 or
+// 1 float32.  af_trace_pick_grid: the most workgroups a launch starts
+hipError_t af_launch_trace_pick(const af::TracePickParams* P, int ncomp, int dtype, hipStream_t stream);
+int af_trace_pick_grid();
 }

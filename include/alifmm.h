@@ -568,6 +568,73 @@ int alifmm_trace_fir(alifmm_ctx* ctx, int64_t ntrace, int nt, int ncomp, const d
 int alifmm_trace_spectral(alifmm_ctx* ctx, int64_t ntrace, int nt, int ncomp, int dtype, const void* in, int nfft,
                           int resp_comp, const double* resp, int analytic, void* out);
 
+/* Time-of-flight picks: per trace the peak of the envelope inside a gate, or its onset, refined to a
+ * fraction of a sample, with the runner-up as a measure of ambiguity; on the device, from traces the
+ * caller holds, optionally through alifmm_trace_spectral's filter without the filtered traces ever
+ * leaving the device.  It makes the measured times the inversion entry points take
+ * (measured - computed).
+ *   in                 [ntrace][nt][ncomp], ncomp 1 (real) or 2 (re, im interleaved)
+ *   dtype              0 float64, 1 float32
+ *   filter             0: pick on in as given; nfft, resp_comp and analytic must be 0 and resp NULL.
+ *                      1: pick on what alifmm_trace_spectral(ntrace, nt, ncomp, dtype, in, nfft,
+ *                      resp_comp, resp, analytic) returns (complex, of the same dtype), with its
+ *                      limits (nt <= ALIFMM_FFT_MAX); the picks are, to the bit, those of filter 0 on
+ *                      that output
+ *   gate_lo, gate_hi   int32 [ntrace]: the trace's gate, samples lo <= n < hi; 0 <= lo and hi <= nt;
+ *                      lo >= hi: the trace is not asked for
+ *   mode               0 peak, 1 onset
+ *   frac               mode 1: the onset's threshold as a fraction of the peak amplitude, 0 < frac <= 1
+ *   guard              >= 0: the runner-up lies more than guard samples from the peak
+ *   pos, amp, amp2     float64 [ntrace]: the pick in samples (seconds: t0 + pos / fs), the peak's and
+ *                      the runner-up's amplitude
+ *   idx, idx2, flags   int32 [ntrace]: the peak's and the runner-up's sample, the flags below
+ * Per trace, all in float64, operations in the order written, no contraction (x the picked traces:
+ * in, or the filter's output):
+ *   energy     e[n] = (re * re) + (im * im), x * x for real data; a float32 sample converts exactly
+ *   candidate  a sample of the gate whose e is neither NaN nor +-inf (a test on the bits).  Any other
+ *              sample in the gate sets flag 16 and is not picked
+ *   peak       idx = the maximum over the gate's candidates of the total order "larger e first, of
+ *              equal e the lower n"; amp = sqrt(e[idx]), correctly rounded.  No candidate, or
+ *              e[idx] == 0: flag 2, idx = idx2 = -1, pos = NaN, amp = amp2 = 0, nothing else
+ *   runner-up  idx2 = the maximum of the same order over the gate's candidates with
+ *              |n - idx| > guard; amp2 = sqrt(e[idx2]); none: idx2 = -1, amp2 = 0.  A maximum, so no
+ *              summation order enters; amp2 / amp near 1 marks a cycle skip or a second echo
+ *   mode 0     m = idx.  If 0 < m < nt - 1 and e[m - 1] and e[m + 1] are neither NaN nor +-inf (they
+ *              may lie outside the gate): a- = sqrt(e[m - 1]), a0 = amp, a+ = sqrt(e[m + 1]); if
+ *              a- <= a0, a+ <= a0 and den = (a- - (2 * a0)) + a+ < 0: delta = (0.5 * (a- - a+)) / den
+ *              (the vertex of the parabola through the three amplitudes).  In every other case
+ *              delta = 0 and flag 4.  Flag 8 if m == lo or m == hi - 1 (the gate cut the echo)
+ *   mode 1     thr = (frac * frac) * e[idx]; m = the lowest candidate n of the gate with e[n] >= thr
+ *              (idx is one).  If m > 0, e[m - 1] is neither NaN nor +-inf and e[m - 1] < thr:
+ *              at = sqrt(thr), am = sqrt(e[m]), a- = sqrt(e[m - 1]), den = am - a-; if den > 0:
+ *              delta = -((am - at) / den) (where the line through the two amplitudes meets the
+ *              threshold).  In every other case delta = 0 and flag 4.  Flag 8 if m == lo
+ *   position   pos = (double)m + delta
+ *   no gate    lo >= hi: flag 1 alone, the outputs as under flag 2
+ * flags: 1 no gate, 2 nothing to pick, 4 unrefined, 8 at the gate's edge, 16 a non-finite sample in
+ * the gate.  The two combines of the reduction (the maximum of two keys, the lower of two indices;
+ * csrc/trace_pick_term.h) are associative and commutative, so a trace's picks depend on nothing but
+ * that trace, its gate and mode, frac, guard, and are bit-reproducible between calls.  The numpy
+ * restatement is tests/trace_pick_ref.py, the host replay of the kernel's code
+ * tests/trace_pick_sim.cpp.
+ * ALIFMM_E_ARG with a message, the context staying usable and no output written: a NULL pointer
+ * (resp excepted); ntrace < 1; nt < 1; ncomp not 1 or 2; dtype, filter or mode not 0 or 1; frac
+ * outside (0, 1] in mode 1; guard < 0; a gate with lo < 0 or hi > nt; more traces than 64-bit byte
+ * offsets hold; filter 0 with nfft, resp_comp or analytic not 0 or resp given; filter 1: every
+ * refusal of alifmm_trace_spectral.
+ * Needs no model.  Upload, the filter's kernel (filter 1), one pick kernel, a download of 36 bytes
+ * per trace; the traces live in alifmm_trace_spectral's grow-only device buffers, the gates and the
+ * outputs in three more, freed with the context.  All trace offsets are 64-bit.
+ * alifmm_get_option, of the last call: "trace_pick_upload_ms" (host -> device copies),
+ * "trace_pick_filter_ms" (the filter's kernel; 0 with filter 0), "trace_pick_kernel_ms" (the pick
+ * kernel), "trace_pick_download_ms" (the device -> host copies); "trace_pick_grid", the most
+ * workgroups a launch starts (a constant of the build; a workgroup picks 4 traces at a time, one
+ * per wavefront, and walks the rest with the grid's stride).  One GPU. */
+int alifmm_trace_pick(alifmm_ctx* ctx, int64_t ntrace, int nt, int ncomp, int dtype, const void* in, int filter, int nfft,
+                      int resp_comp, const double* resp, int analytic, const int32_t* gate_lo, const int32_t* gate_hi,
+                      int mode, double frac, int guard, double* pos, double* amp, int32_t* idx, double* amp2,
+                      int32_t* idx2, int32_t* flags);
+
 /* Pulse-aware least-squares imaging: alifmm_tfm_lsq with the pulse in the operator,
  * min |P A x - d|^2 + damp^2 |x|^2 + smooth^2 |D x|^2 by CGLS from x = 0.
  *   subgrid ... tol    as in alifmm_tfm_lsq
