@@ -108,6 +108,7 @@ def _load():
                                       _p]),
             "alifmm_cr_math": (_i, [_p, _i, _i, _l, _p, _p, _p]),
             "alifmm_fouds18_band": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
+            "alifmm_fouds18_band_lanes": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
             "alifmm_comm_unique_id": (_i, [_p]),
             "alifmm_comm_init_rank": (_i, [_p, _i, _i, _p, _p]),
             "alifmm_comm_init_all": (_i, [_p, _i, _p]),
@@ -965,7 +966,9 @@ class Context:
         return out
 
     def local_ops(self, op, ttn, nsts, iz, ix, dnx, dnz, nnz_arg, nnx_arg, cveln, cvelpn, cvm, cstif, tab):
-        """Batched update() (op 0) / fouds18_A() (op 1) on (n, pz, px) patches."""
+        """Batched update() (op 0) / fouds18_A() (op 1) on (n, pz, px) patches.  Test entries, same
+        inputs and bits (include/alifmm.h): op 3 update() on the kernels' register neighbourhood,
+        op 4 the same selected over a wavefront, op 5 fouds18_A() on four lanes per case."""
         ttn = _c64(ttn)
         n, pz, px = ttn.shape
         nsts = _ci32(nsts)
@@ -995,16 +998,18 @@ class Context:
                   "cr_math")
         return (out, out2) if fn == 4 else out
 
-    def fouds18_band(self, ttn, nsts, iz, ix, dnx, dnz, nnz_arg, nnx_arg, mz, mx, quant=0):
+    def fouds18_band(self, ttn, nsts, iz, ix, dnx, dnz, nnz_arg, nnx_arg, mz, mx, quant=0, lanes=False):
         """fouds18_A() as the band kernel evaluates it: material of resident-model cell (mz, mx)
-        through the per-material record and precomputed slownesses (alifmm_fouds18_band)."""
+        through the per-material record and precomputed slownesses (alifmm_fouds18_band).
+        lanes: on four lanes per case, as the kernel's fallback rounds (alifmm_fouds18_band_lanes)."""
         ttn = _c64(ttn)
         n, pz, px = ttn.shape
         out = np.empty(n)
         nsts = _ci32(nsts)
         args = [_ci32(iz), _ci32(ix), _c64(dnx), _c64(dnz), _ci32(nnz_arg), _ci32(nnx_arg), _ci32(mz), _ci32(mx)]
-        self._chk(lib().alifmm_fouds18_band(self._h, n, pz, px, _ptr(ttn), _ptr(nsts), *[_ptr(a) for a in args],
-                                            int(quant), _ptr(out)), "fouds18_band")
+        fn = lib().alifmm_fouds18_band_lanes if lanes else lib().alifmm_fouds18_band
+        self._chk(fn(self._h, n, pz, px, _ptr(ttn), _ptr(nsts), *[_ptr(a) for a in args], int(quant), _ptr(out)),
+                  "fouds18_band")
         return out
 
 

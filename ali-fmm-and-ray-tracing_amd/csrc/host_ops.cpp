@@ -2,6 +2,7 @@
 // operators of a batch of patches (local_ops), the band kernel's fouds18 fallback (fouds18_band) and
 // the correctly rounded trigonometric functions themselves (cr_math).
 #include <cstring>
+#include <limits>
 
 #include "host_internal.h"
 
@@ -48,15 +49,45 @@ extern "C" int alifmm_cr_math(alifmm_ctx* ctx, int fn, int lds_tables, int64_t n
   return ALIFMM_OK;
 }
 
+// The test entries (ops 3..6) read each patch as the field kernels read their grids, so their
+// arguments are checked as no module-level call needs: the cell inside the patch, update()'s and
+// fouds18_A()'s column bound inside it (rows past it read -1 / 0), and a finite ttn at every valid
+// node (NaN is the HBM grids' code for a far node: a NaN there would turn the node invalid).
+static int test_form_args(alifmm_ctx* ctx, const char* who, int n, int pz, int px, const double* ttn,
+                          const int32_t* nsts, const int32_t* iz, const int32_t* ix, const int32_t* nnx_arg) {
+  const size_t pn = (size_t)pz * px;
+  for (int k = 0; k < n; k++) {
+    if (iz[k] < 0 || iz[k] >= pz || ix[k] < 0 || ix[k] >= px || nnx_arg[k] > px)
+      return fail(ctx, ALIFMM_E_ARG, "%s: case %d: cell (%d, %d) or nnx %d outside the %d x %d patch", who, k, iz[k],
+                  ix[k], nnx_arg[k], pz, px);
+    for (size_t i = k * pn; i < (k + 1) * pn; i++)
+      if (nsts[i] >= 0 && !std::isfinite(ttn[i]))
+        return fail(ctx, ALIFMM_E_ARG, "%s: case %d: ttn is not finite at a valid node (%d, %d)", who, k,
+                    (int)((i - k * pn) / px), (int)((i - k * pn) % px));
+  }
+  return ALIFMM_OK;
+}
+
 extern "C" int alifmm_local_ops(alifmm_ctx* ctx, int op, int n, int pz, int px, const double* ttn, const int32_t* nsts,
                                 const int32_t* iz, const int32_t* ix, const double* dnx, const double* dnz, const int32_t* nnz_arg,
                                 const int32_t* nnx_arg, const double* cell_veln, const int64_t* cell_velpn, const double* cell_vm,
                                 const int64_t* cell_stif, const double* tab, int ncol, double* out) {
-  if (!ctx || (op != 0 && op != 1) || n < 0 || pz < 1 || px < 1 || ncol < 1)
-    return fail(ctx, ALIFMM_E_ARG, "local_ops: bad args");
+  if (!ctx) return ALIFMM_E_ARG;
+  if (op != 0 && op != 1 && (op < 3 || op > 5))
+    return fail(ctx, ALIFMM_E_ARG, "local_ops: op %d (0, 1; test entries 3, 4, 5)", op);
+  if (n < 0 || pz < 1 || px < 1 || ncol < 1) return fail(ctx, ALIFMM_E_ARG, "local_ops: bad args");
   if (n == 0) return ALIFMM_OK;
-  HIPCHK(hipSetDevice(ctx->device));
   const size_t pn = (size_t)pz * px;
+  std::vector<double> coded;  // ops 3, 4: the patches as the HBM grids hold them
+  if (op >= 3) {
+    if (int rc = test_form_args(ctx, "local_ops", n, pz, px, ttn, nsts, iz, ix, nnx_arg)) return rc;
+    if (op != 5) {
+      coded.resize(pn * n);
+      for (size_t i = 0; i < coded.size(); i++) coded[i] = nsts[i] >= 0 ? ttn[i] : std::numeric_limits<double>::quiet_NaN();
+      ttn = coded.data();
+    }
+  }
+  HIPCHK(hipSetDevice(ctx->device));
   std::vector<int> vp(n);
   for (int k = 0; k < n; k++) vp[k] = (int)cell_velpn[k];
   std::vector<double> st;
@@ -119,11 +150,13 @@ extern "C" int alifmm_local_ops(alifmm_ctx* ctx, int op, int n, int pz, int px, 
   return ALIFMM_OK;
 }
 
-extern "C" int alifmm_fouds18_band(alifmm_ctx* ctx, int n, int pz, int px, const double* ttn, const int32_t* nsts,
-                        const int32_t* iz, const int32_t* ix, const double* dnx, const double* dnz,
-                        const int32_t* nnz_arg, const int32_t* nnx_arg, const int32_t* mz, const int32_t* mx, int quant,
-                        double* out) {
-  if (!ctx || !ctx->have_model || n < 0 || pz < 1 || px < 1 || (quant != 0 && quant != 1))
+// op 2: one lane per case (alifmm_fouds18_band); op 6: four lanes per case (alifmm_fouds18_band_lanes)
+static int fouds18_band_op(alifmm_ctx* ctx, int op, int n, int pz, int px, const double* ttn, const int32_t* nsts,
+                           const int32_t* iz, const int32_t* ix, const double* dnx, const double* dnz,
+                           const int32_t* nnz_arg, const int32_t* nnx_arg, const int32_t* mz, const int32_t* mx,
+                           int quant, double* out) {
+  if (!ctx) return ALIFMM_E_ARG;
+  if (!ctx->have_model || n < 0 || pz < 1 || px < 1 || (quant != 0 && quant != 1))
     return fail(ctx, ALIFMM_E_ARG, "fouds18_band: bad args or no model");
   if (!ctx->dm.mid || !ctx->dm.mslo)
     return fail(ctx, ALIFMM_E_ARG, "fouds18_band: the model has no per-material table (too many materials)");
@@ -131,6 +164,8 @@ extern "C" int alifmm_fouds18_band(alifmm_ctx* ctx, int n, int pz, int px, const
     if (mz[k] < 0 || mz[k] >= ctx->nz0 || mx[k] < 0 || mx[k] >= ctx->nx0)
       return fail(ctx, ALIFMM_E_ARG, "fouds18_band: model cell %d (%d, %d) outside the grid", k, mz[k], mx[k]);
   if (n == 0) return ALIFMM_OK;
+  if (op == 6)
+    if (int rc = test_form_args(ctx, "fouds18_band", n, pz, px, ttn, nsts, iz, ix, nnx_arg)) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   const size_t pn = (size_t)pz * px;
   // [ttn | dnx | dnz | out] doubles, [nsts | iz | ix | nnz | nnx | mz | mx] ints
@@ -143,7 +178,7 @@ extern "C" int alifmm_fouds18_band(alifmm_ctx* ctx, int n, int pz, int px, const
   }
   af::LocalOpsParams P;
   memset(&P, 0, sizeof P);
-  P.op = 2;
+  P.op = op;
   P.n = n;
   P.pz = pz;
   P.px = px;
@@ -182,4 +217,18 @@ extern "C" int alifmm_fouds18_band(alifmm_ctx* ctx, int n, int pz, int px, const
   dfree(di);
   if (e != hipSuccess) return fail(ctx, ALIFMM_E_HIP, "fouds18_band: %s", hipGetErrorString(e));
   return ALIFMM_OK;
+}
+
+extern "C" int alifmm_fouds18_band(alifmm_ctx* ctx, int n, int pz, int px, const double* ttn, const int32_t* nsts,
+                        const int32_t* iz, const int32_t* ix, const double* dnx, const double* dnz,
+                        const int32_t* nnz_arg, const int32_t* nnx_arg, const int32_t* mz, const int32_t* mx, int quant,
+                        double* out) {
+  return fouds18_band_op(ctx, 2, n, pz, px, ttn, nsts, iz, ix, dnx, dnz, nnz_arg, nnx_arg, mz, mx, quant, out);
+}
+
+extern "C" int alifmm_fouds18_band_lanes(alifmm_ctx* ctx, int n, int pz, int px, const double* ttn, const int32_t* nsts,
+                                         const int32_t* iz, const int32_t* ix, const double* dnx, const double* dnz,
+                                         const int32_t* nnz_arg, const int32_t* nnx_arg, const int32_t* mz,
+                                         const int32_t* mx, int quant, double* out) {
+  return fouds18_band_op(ctx, 6, n, pz, px, ttn, nsts, iz, ix, dnx, dnz, nnz_arg, nnx_arg, mz, mx, quant, out);
 }

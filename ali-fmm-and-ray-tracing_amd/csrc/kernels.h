@@ -134,10 +134,15 @@ struct RayParams {
 };
 
 struct LocalOpsParams {
-  int op;  // 0 update(), 1 fouds18_A(), 2 fouds18_A() as the band kernel runs it (resident model)
+  // 0 update() (update_ref), 1 fouds18_A(), 2 fouds18_A() as the band kernel runs it (resident model);
+  // test entries for the forms the field kernels run: 3 update() on a register neighbourhood
+  // (NbFieldT::load + update_nb), 4 the same selected over a wavefront (update_select_lanes),
+  // 5 fouds18_A() on four lanes (fouds18_part<false>, f18_min, fouds18_combine), 6 the same with
+  // fouds18_part<true> on the resident model
+  int op;
   long n;
   int pz, px;
-  const double* ttn;  // [n][pz][px]
+  const double* ttn;  // [n][pz][px]; ops 3, 4: NaN where nsts < 0 (the HBM grids' coding)
   const int* nsts;
   const int* iz;
   const int* ix;

@@ -33,7 +33,8 @@ AF_DEV double fouds18_slowness(const DevModel& M, const CellMat& cm, int q) {
 // family's candidate number part, -1: all of them; +inf where a family has no candidate), so that
 // four lanes can evaluate one cell and combine their parts (fouds18_combine, the reference's
 // combination :696-897).  Each family's result is a minimum over its candidates (the reference's
-// running min, order-free: no candidate is NaN), so any split gives the same bits.
+// running min, order-free: no candidate is NaN), so any split gives the same bits
+// (tests/test_gpu_local_ops.py: the four-lane split against the oracle, every case bit for bit).
 struct F18Part {
     double m[4];
 };
@@ -704,7 +705,8 @@ AF_DEV double update_ref(const F& f, const DevModel& M, const CellMat& cm, int i
 // selection keeps the reference's order and strict '<', and the chosen stencil's wavefront
 // parameters are carried through the selection instead of a 16-way switch, so a wavefront does
 // not serialise over its lanes' stencil cases.  The triangular stage and the velocity are shared
-// with update_ref.  Bit-identical to update_ref (tools/micro/update_bench checksums, GPU tests).
+// with update_ref.  Bit-identical to update_ref (tests/test_gpu_local_ops.py: this form, the lane
+// form below and update_ref against the oracle over every validity mask and bounds combination).
 // update()'s result is upd_finish() of the stencil stage's outputs: two calls whose stencil
 // stages are equal give the same value (the init kernels' parallel relaxation relies on it)
 struct UpdSel {

@@ -873,7 +873,20 @@ int alifmm_time_between_points(alifmm_ctx* ctx, int n, const double* x1, const d
 /* Evaluate the local operators on n independent neighbourhoods (pz x px patches; rows past pz
  * read as nsts=-1/ttn=0, the reference's padded stage-1 semantics).  op 0: update() :904-1410
  * with the phase table; op 1: fouds18_A() :240-901 with the group table.  Material is given at
- * the target cell only (the operators read nothing else); cell_stif (n x 5) NULL = None. */
+ * the target cell only (the operators read nothing else); cell_stif (n x 5) NULL = None.
+ *
+ * Ops 3, 4 and 5 are test entry points: the same inputs through the forms of the operators that
+ * the field kernels run, each held to the bits of ops 0 / 1 (tests/test_gpu_local_ops.py).
+ *   3  update() on a register neighbourhood: the patch coded as the device grids are (NaN where
+ *      nsts < 0), read by the kernels' 12-point loader with its clamped addresses, then the
+ *      branch-free selection under update()'s bounds (nnz_arg / nnx_arg).
+ *   4  as 3 with the selection spread over one wavefront per case (the exact walks' relax step).
+ *   5  fouds18_A() on four lanes per case, one candidate of each stencil family per lane,
+ *      reduced and combined as in the band kernel's fallback rounds.
+ * (2 and 6 are alifmm_fouds18_band and alifmm_fouds18_band_lanes.)  The kernels' own lane-local
+ * slot loaders from LDS are private to them and are not reached from here.
+ * ALIFMM_E_ARG: any other op; for ops 3..5 also a cell outside its patch, an nnx_arg above px, or
+ * a ttn that is not finite at a node with nsts >= 0.  The context stays usable. */
 int alifmm_local_ops(alifmm_ctx* ctx, int op, int n, int pz, int px, const double* ttn, const int32_t* nsts,
                      const int32_t* iz, const int32_t* ix, const double* dnx, const double* dnz,
                      const int32_t* nnz_arg, const int32_t* nnx_arg, const double* cell_veln,
@@ -897,6 +910,14 @@ int alifmm_fouds18_band(alifmm_ctx* ctx, int n, int pz, int px, const double* tt
                         const int32_t* iz, const int32_t* ix, const double* dnx, const double* dnz,
                         const int32_t* nnz_arg, const int32_t* nnx_arg, const int32_t* mz, const int32_t* mx,
                         int quant, double* out);
+
+/* Test entry point (op 6): alifmm_fouds18_band on four lanes per case, the candidates split and
+ * reduced as in the band kernel's fallback rounds.  Same arguments, same bits; the argument
+ * checks of alifmm_local_ops ops 3..5 on top of alifmm_fouds18_band's (ALIFMM_E_ARG: no model). */
+int alifmm_fouds18_band_lanes(alifmm_ctx* ctx, int n, int pz, int px, const double* ttn, const int32_t* nsts,
+                              const int32_t* iz, const int32_t* ix, const double* dnx, const double* dnz,
+                              const int32_t* nnz_arg, const int32_t* nnx_arg, const int32_t* mz,
+                              const int32_t* mx, int quant, double* out);
 
 /* ---- RCCL gather of resident fields onto one GPU (replaces the reference's result return over
  * multiprocessing queue2: parallel_TTF :3610, parallel_TTF_finer_grid :3659, parallel_TTF_rays

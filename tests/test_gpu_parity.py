@@ -86,8 +86,19 @@ def test_library_is_the_hip_build():
     assert b"gfx950" in _alifmm.lib().alifmm_version()
 
 
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
 def test_local_ops_vs_reference_vectors(golden, ctx, envelope):
+    """The reference's own vectors (numba with glibc's trig) at the bar from before the device's trig
+    was correctly rounded, and beside it the bar that holds since: every case equals the correctly
+    rounded build of the oracle in every bit (tests/test_gpu_local_ops.py holds every other form of
+    the two operators to the same)."""
+    import local_ops_cases as LC
+
     g = golden("local_ops")
+    cu, cf = LC.golden_sets(g)
     n = len(g["u_out"])
     a = g["u_args"]
     out = ctx.local_ops(0, g["u_ttn"], g["u_nsts"].astype(np.int32), a[:, 0], a[:, 1], a[:, 2], a[:, 2], a[:, 3],
@@ -98,6 +109,8 @@ def test_local_ops_vs_reference_vectors(golden, ctx, envelope):
     rel = np.abs(out - ref) / np.maximum(np.abs(ref), 1e-300)
     envelope["local_ops_update"] = {"exact_frac": float(exact / n), "rel_max": float(rel.max())}
     assert exact >= 0.99 * n and rel.max() <= 1e-12, (exact, n, rel.max())
+    cr = LC.golden_reference(g, cu)
+    assert np.array_equal(_bits(out), _bits(cr)), ("update", int(np.sum(_bits(out) != _bits(cr))), n)
     f = g["f_args"]
     m = len(g["f_out"])
     outf = ctx.local_ops(1, g["f_ttn"], g["f_nsts"].astype(np.int32), f[:, 0], f[:, 1], f[:, 2], f[:, 2],
@@ -108,6 +121,8 @@ def test_local_ops_vs_reference_vectors(golden, ctx, envelope):
     rel = np.abs(outf - reff) / np.maximum(np.abs(reff), 1e-300)
     envelope["local_ops_fouds18"] = {"exact_frac": float(exact / m), "rel_max": float(rel.max())}
     assert exact >= 0.99 * m and rel.max() <= 1e-12, (exact, m, rel.max())
+    cr = LC.golden_reference(g, cf)
+    assert np.array_equal(_bits(outf), _bits(cr)), ("fouds18", int(np.sum(_bits(outf) != _bits(cr))), m)
 
 
 def test_time_between_points_vs_reference_vectors(golden, ctx, envelope):
@@ -409,8 +424,12 @@ def test_band_fouds18_path_vs_oracle(golden, ctx, envelope):
     """fouds18_A() as the band kernel runs it (the material record + the per-material slownesses
     precomputed by mat_slowness_kernel, fouds18<true>) against the oracle's fouds18_A with the
     same cell's material, on the reference's own neighbourhoods, for both material views (subgrid
-    1 as is; subgrid > 1 with finer_grid_n's int32 orientation / float32 vel_map)."""
+    1 as is; subgrid > 1 with finer_grid_n's int32 orientation / float32 vel_map).  Beside that bar
+    (glibc's trig), every case equals the correctly rounded build of the oracle in every bit."""
+    import local_ops_cases as LC
+
     g = golden("local_ops")
+    cf = LC.golden_sets(g)[1]
     vt = W.default_table()
     n = len(g["f_out"])
     f = g["f_args"]
@@ -437,6 +456,8 @@ def test_band_fouds18_path_vs_oracle(golden, ctx, envelope):
             envelope["fouds18_band_%s_q%d" % (name, quant)] = {"exact_frac": float(np.mean(out == ref)),
                                                                "rel_max": float(rel.max())}
             assert np.mean(out == ref) >= 0.99 and rel.max() <= EXACT, (name, quant, np.mean(out == ref), rel.max())
+            cr = LC.resident_reference("parity_" + name, (veln, velpn, vm, sd), quant, cf, mz, mx, vt)
+            assert np.array_equal(_bits(out), _bits(cr)), (name, quant, int(np.sum(_bits(out) != _bits(cr))), n)
 
 
 def test_weld_example_end_to_end(golden, A, envelope, tmp_path):
